@@ -12,11 +12,15 @@ A "step" is one `env.step(actions)` over all environments of the rank: one pass 
 Workload at N=1: BASELINE.json configs[1] = Unitree-A1 Velocity-Rough, 4096 envs, random actions
 ~U(-1,1) (the `scripts/tools/random_agent.py:68` distribution) already resident in HBM.  Environments
 shard embarrassingly: every rank owns its own 4096 envs, seed = 42 + rank (as `train.py:148`); the only
-collective is one RCCL all-reduce of the packed episode-metric vector after the timed region ("weak" scaling).
+collective is one RCCL all-reduce of the packed episode-metric vector after the timed region (`--full`; "weak" scaling).
 `--gpus N` must equal the number of ranks that actually run: without WORLD_SIZE in the environment the script
 re-executes itself under `torch.distributed.run` with N ranks; with it, a mismatch is an error.
 
-Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes per launch
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`); `--dump-outputs DIR` also writes what the last timed step returned (observations, rewards, dones, episode log)
+as .npy files, for output-for-output comparison of two builds on identical seeded inputs.  `--full` adds everything else below:
+the window statistics, the episode-metric collective, `roofline`, the large-batch legs and `cpu_baseline`.
+`roofline.achieved` = algorithmic bytes per launch
 (3.4 KB per env-step x 4096 envs) / mean kernel duration measured with HIP events
 on the launch stream; `cpu_baseline` = the same env-step program compiled for the host (tests/emu: the source
 hipcc compiles, g++ -O3 -march=native) as a CPU program - one environment per thread, one pinned thread per physical
@@ -47,13 +51,21 @@ def parse_args(argv=None):
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--task", type=str, default="RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0")
     ap.add_argument("--preroll", type=int, default=300, help="untimed steps before the warm-up, after the episode clocks were randomised")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed env.step() returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: window statistics, the episode-metric collective, kernel time + roofline, "
+                         "the large-batch legs and the CPU baselines (the options below act only with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--large-batch-envs", type=int, default=65536, help="0: skip the large-batch legs (rank 0 of a 1-GPU run, after the timed region)")
     ap.add_argument("--mid-batch-envs", type=int, default=8192, help="second such leg (two sub-lanes per limb at this size); skipped with --large-batch-envs 0")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU work the baseline leg may spend on the lane-program port")
     ap.add_argument("--cpu-oracle-envs", type=int, default=256)
     ap.add_argument("--cpu-oracle-steps", type=int, default=10)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -145,13 +157,15 @@ def main():
 
     for i in range(args.warmup):
         env.step(ring[i % 32])
-    ep_before = env.episode_length_buf.clone()
+    ep_before = env.episode_length_buf.clone() if args.full else None
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        env.step(ring[i % 32])
+        last = env.step(ring[i % 32])
     barrier()
     elapsed_rank = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before anything else launches: the observations are views of the env's ring buffers
+        dump_outputs(args.dump_outputs, last)
     elapsed = elapsed_rank
     per_rank = [N * args.steps / elapsed_rank]
     if use_dist:
@@ -161,6 +175,73 @@ def main():
         per_rank = [N * args.steps / float(x.item()) for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    value = world * N * args.steps / elapsed
+    robot = robot_name(args.task)
+    out = {
+        "metric": f"env-steps/sec (whole node) at {N} envs/GPU, {robot} Velocity-{'Flat' if 'Flat' in args.task else 'Rough'}",
+        "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.task}, {N} envs/GPU, random actions U(-1,1), seed 42+rank", "envs_per_gpu": N,
+                   "parallelism": f"env-shard x{world}",
+                   # which step kernel ran: the one specialised on this task (csrc/env_spec.h, id of tools/gen_specs.py) or the term-stack interpreter
+                   "step_kernel": env.step_kernel,
+                   "envs_per_wavefront": env._native.envs_per_wavefront()},
+        "rccl_ranks": dist.get_world_size() if use_dist else 1, "collective_backend": ("gloo (RL_BENCH_SHARE_GPU self-test)" if share else "nccl (RCCL)") if use_dist else None,
+        "per_rank_env_steps_per_s": per_rank,
+    }
+    if args.full:
+        full_figures(args, env, ring, ep_before, out, dev, rank, world)
+    env.close()
+    if use_dist:
+        dist.destroy_process_group()
+    if rank == 0:
+        # the JSON line is the LAST thing on stdout: RCCL prints a version banner through C stdio, which a pipe buffers until exit
+        import ctypes
+
+        sys.stdout.flush()
+        ctypes.CDLL(None).fflush(None)
+        print(json.dumps(out), flush=True)
+
+
+def robot_name(task: str) -> str:
+    return task.replace("RobotLab-Isaac-Velocity-", "").replace("-v0", "").split("-", 1)[1].replace("Unitree-", "")
+
+
+# caps the files of --dump-outputs; beyond it a fixed, seeded sample of the environments is written
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, result) -> None:
+    """`result` = (obs, reward, terminated, time_outs, extras) of env.step(), written as float32 .npy files, one row per env:
+    obs_policy, obs_critic, reward, terminated and time_outs (0 / 1); extras_log.npy is extras["log"] as one float64 vector in
+    the log's key order.  When the per-env arrays exceed DUMP_MAX_BYTES, the same seeded sample of rows is taken from each and
+    env_rows.npy lists them."""
+    import numpy as np
+
+    obs, rew, term, tout, extras = result
+    arrays = {"obs_policy": obs["policy"], "obs_critic": obs["critic"], "reward": rew, "terminated": term, "time_outs": tout}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = len(arrays["reward"])
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_MAX_BYTES - (1 << 16)) // (row_bytes + 8), replace=False))  # + env_rows, the log
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        np.save(os.path.join(out_dir, "env_rows.npy"), rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log = extras.get("log")
+    if log is not None:
+        np.save(os.path.join(out_dir, "extras_log.npy"), np.array([float(log[k]) for k in log], dtype=np.float64))
+
+
+def full_figures(args, env, ring, ep_before, out, dev, rank, world) -> None:
+    """What `--full` adds to the result line `out`: the window statistics, the reduced episode-metric vector, kernel time and
+    roofline, then (rank 0 of a 1-GPU run) the large-batch legs and the CPU baselines."""
+    import torch
+
+    N, A = args.num_envs, env.num_actions
     # what the timed window held (a cold 20-step window after reset looks different from steady state: robots still
     # falling, no resets): envs that were reset inside it, and how many bodies touch the ground at its end
     envs_reset = int((env.episode_length_buf < ep_before + args.steps).sum())
@@ -201,23 +282,12 @@ def main():
             prof_src = tr.get("source", "profiles/traffic.json")
     except (OSError, ValueError, KeyError):
         pass
-    value = world * N * args.steps / elapsed
-    robot = args.task.replace("RobotLab-Isaac-Velocity-", "").replace("-v0", "").split("-", 1)[1].replace("Unitree-", "")
+    robot = robot_name(args.task)
     per_step = ALGO_BYTES_PER_ENV_STEP.get(robot, ALGO_BYTES_PER_ENV_STEP["Go2W" if A == 16 else "A1"])  # other quadrupeds: as their Unitree twin
     algo_bytes = (per_step - (2 * 187 * 4 if "Flat" in args.task else 0)) * N
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-    out = {
-        "metric": f"env-steps/sec (whole node) at {N} envs/GPU, {robot} Velocity-{'Flat' if 'Flat' in args.task else 'Rough'}",
-        "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.task}, {N} envs/GPU, random actions U(-1,1), seed 42+rank", "envs_per_gpu": N,
-                   "parallelism": f"env-shard x{world}",
-                   # which step kernel ran: the one specialised on this task (csrc/env_spec.h, id of tools/gen_specs.py) or the term-stack interpreter
-                   "step_kernel": env.step_kernel,
-                   "envs_per_wavefront": env._native.envs_per_wavefront()},
-        "rccl_ranks": dist.get_world_size() if use_dist else 1, "collective_backend": ("gloo (RL_BENCH_SHARE_GPU self-test)" if share else "nccl (RCCL)") if use_dist else None,
-        "per_rank_env_steps_per_s": per_rank, "envs_behind_reduced_log": float(log_vec[LOG_SLOT_NUM_ENVS]),
+    out.update({
+        "envs_behind_reduced_log": float(log_vec[LOG_SLOT_NUM_ENVS]),
         "window": {"envs_reset_in_window": envs_reset, "mean_bodies_in_contact_at_end": bodies_in_contact,
                    "preroll_steps": args.preroll,
                    "note": "rank 0; episode clocks randomised over [0, 1000) and `preroll_steps` untimed steps before the warm-up: steady state"},
@@ -227,7 +297,7 @@ def main():
                      # `achieved` / `kernel_ms` are measured live in this run; `traffic` and the cycle breakdown are NOT: they are the
                      # rocprofv3 PMC passes of an earlier run of the same command, read from the file named here
                      "offline": {"fields": ["traffic", "wavefront_cycle_breakdown"], "source": prof_src} if traffic is not None else None},
-    }
+    })
     env.close()
     if rank == 0 and world == 1 and args.large_batch_envs > N:
         out["large_batch"] = large_batch(args.task, args.large_batch_envs, dev)
@@ -239,15 +309,6 @@ def main():
                 lb["roofline_frac"] = lb["achieved_GBps"] / HBM_PEAK_GBS
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.task, N, args.cpu_seconds, args.cpu_oracle_envs, args.cpu_oracle_steps)
-    if use_dist:
-        dist.destroy_process_group()
-    if rank == 0:
-        # the JSON line is the LAST thing on stdout: RCCL prints a version banner through C stdio, which a pipe buffers until exit
-        import ctypes
-
-        sys.stdout.flush()
-        ctypes.CDLL(None).fflush(None)
-        print(json.dumps(out), flush=True)
 
 
 def large_batch(task: str, n_envs: int, dev: str) -> dict:

@@ -19,9 +19,7 @@ This test closes that hole with Lagrange's equations:
   p'' = R (a_lin + omega_b x v_b) (the spatial acceleration's linear part is that of the body point passing the frame origin).
 
 The residual of Lagrange's equations with the oracle's accelerations must vanish to 1e-6 of the largest term, for random
-configurations, base twists, joint rates and joint torques of A1 and G1.  Needs the reference's URDF files: skipped where absent."""
-import os
-
+configurations, base twists, joint rates and joint torques of A1 and G1 (the reference's URDF files, committed under tests/golden/urdf)."""
 import numpy as np
 import pytest
 
@@ -29,9 +27,8 @@ from oracle import spatial as sp
 from oracle.physics import Physics
 from robot_lab_amd.desc import arr
 from robot_lab_amd.scene import load_bundle
-from test_urdf_energy import ROBOTS, Urdf
+from test_urdf_energy import Urdf, committed_urdf
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(ROBOTS), reason="needs the reference's URDF files")
 CASES = [("RobotLab-Isaac-Velocity-Flat-Unitree-A1-v0", "a1_description/urdf/a1.urdf"),
          ("RobotLab-Isaac-Velocity-Flat-Unitree-G1-v0", "g1_description/urdf/g1_29dof_rev_1_0.urdf")]
 
@@ -125,7 +122,7 @@ def test_oracle_accelerations_satisfy_lagranges_equations(task, urdf):
     wb1 = np.einsum("nji,nj->ni", R0, st["root_ang_vel"])                                   # nu+ in the frame of time t (oracle/physics.py: rotated with
     vb1 = np.einsum("nji,nj->ni", R0, st["root_lin_vel"]) - dt * np.cross(nu0[:, :3], nu0[:, 3:6])  # the OLD orientation, reference point shifted by dt w x v)
     nud = (np.concatenate([wb1, vb1, st["qd"]], -1) - nu0) / dt
-    U = Urdf(os.path.join(ROBOTS, urdf))
+    U = Urdf(committed_urdf(urdf))
     names = list(desc.joint_names)
     worst = 0.0
     for e in range(N):

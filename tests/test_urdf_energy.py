@@ -11,7 +11,8 @@ For random joint positions, joint velocities and base twists the kinetic energy 
 Equal energies for arbitrary (q, nu) mean equal mass matrices: masses, COMs, inertia tensors and their frames, joint origins,
 orientations, axes, the tree and the joint naming all agree with the file the reference loads (`assets/unitree.py:24,76,126,470`).
 Total mass, COM and the whole-robot inertia tensor about the base origin follow as special cases and are checked by name.
-Needs /root/reference (the URDFs are not copied into this repository): skipped where it is absent."""
+The four URDFs of CASES are verbatim copies of the reference's files under tests/golden/urdf (pinned to the originals where the
+reference checkout exists); the every-robot test needs the reference's cfg classes and is skipped where they are absent."""
 import os
 import xml.etree.ElementTree as ET
 
@@ -22,15 +23,15 @@ from oracle.physics import Physics
 from oracle import spatial as sp
 from robot_lab_amd.desc import arr
 from robot_lab_amd.scene import load_bundle
+from robot_lab_amd.shims import REFERENCE_SOURCE
 
-ROBOTS = "/root/reference/source/robot_lab/data/Robots/unitree"
+ROBOTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "urdf")  # the CASES' URDFs (file names as in the reference)
 CASES = [  # task id, URDF the reference's ArticulationCfg names
     ("RobotLab-Isaac-Velocity-Flat-Unitree-A1-v0", "a1_description/urdf/a1.urdf"),
     ("RobotLab-Isaac-Velocity-Flat-Unitree-Go2-v0", "go2_description/urdf/go2_description.urdf"),
     ("RobotLab-Isaac-Velocity-Flat-Unitree-Go2W-v0", "go2w_description/urdf/go2w_description.urdf"),
     ("RobotLab-Isaac-Velocity-Flat-Unitree-G1-v0", "g1_description/urdf/g1_29dof_rev_1_0.urdf"),
 ]
-pytestmark = pytest.mark.skipif(not os.path.isdir(ROBOTS), reason="needs the reference's URDF files")
 
 
 def _vec(s, default):
@@ -99,12 +100,18 @@ class Urdf:
 
 @pytest.mark.parametrize("task,urdf", CASES)
 def test_kinetic_energy_matches_the_urdf(task, urdf):
-    _check(task, os.path.join(ROBOTS, urdf))
+    _check(task, committed_urdf(urdf))
 
 
+def committed_urdf(urdf):
+    """The committed copy of the reference's `<robot>_description/urdf/<file>.urdf`."""
+    return os.path.join(ROBOTS, os.path.basename(urdf))
+
+
+@pytest.mark.skipif(not os.path.isdir(REFERENCE_SOURCE), reason="needs the reference's cfg classes and URDF files")
 def test_every_committed_robot_matches_its_urdf():
     """The same for every robot with a committed bundle; the URDF path comes from the reference's own ArticulationCfg
-    (`cfg.scene.robot.spawn.asset_path`, parsed through the shims)."""
+    (`cfg.scene.robot.spawn.asset_path`, parsed through the shims).  The committed copies of CASES must be those files, byte for byte."""
     import glob
 
     from robot_lab_amd import shims
@@ -115,14 +122,19 @@ def test_every_committed_robot_matches_its_urdf():
 
     from robot_lab_amd.scene import DATA_DIR
 
-    seen = 0
+    seen, pinned = 0, set()
     for path in sorted(glob.glob(os.path.join(DATA_DIR, "RobotLab-Isaac-Velocity-Flat-*.json"))):
         task = os.path.basename(path)[:-5]
         urdf = parse_env_cfg(task, device="cpu", num_envs=4).scene.robot.spawn.asset_path
         assert urdf.endswith(".urdf") and os.path.isfile(urdf), (task, urdf)
         _check(task, urdf)
         seen += 1
+        if os.path.isfile(committed_urdf(urdf)):
+            with open(committed_urdf(urdf), "rb") as a, open(urdf, "rb") as b:
+                assert a.read() == b.read(), f"{committed_urdf(urdf)} is not a copy of {urdf}"
+            pinned.add(os.path.basename(urdf))
     assert seen >= 18
+    assert pinned == {os.path.basename(u) for _, u in CASES}, pinned
 
 
 def _check(task, urdf_path):
