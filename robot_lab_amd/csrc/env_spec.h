@@ -35,6 +35,7 @@ struct ObsSpec {  // constexpr twin of ObsTab
 struct NoSpec {  // the interpreter
   static constexpr bool ON = false;
   static constexpr int ID = 0;
+  static constexpr uint32_t SLOT_VALID = ~0u;  // every sphere slot may hold a sphere: the interpreter walks them all
 };
 
 // joints of limb k (bit j: the lane's joint slot j - [0, CL) limb joints, [CL, CL + NW) trunk joints, which limb 0 accounts for) that
@@ -76,6 +77,28 @@ inline int table_axis_kind(const LT& L, int j) {
   }
   return kind;
 }
+// The sphere-slot census: SP::SLOT_VALID is the task's TablesT::slot_valid (bit g * SPL + s: some limb has a collision sphere in slot s of
+// link group g) as a constant.  A slot that NO link group of a walk holds - A1 fills two of TopoQuad3's three slots in every group; Go2, Go2W
+// and G1 fill every slot in some group of their 16-lane iteration - is dropped from that walk at compile time (env_step.h slot_live): no
+// sphere centre, no heightfield load, no patch evaluation, no contact copy, no stash traffic (A1 Rough 4096: 32.5 -> 31.2 us,
+// profiles/r07c_ab_parent_vs_census.txt).  A slot some groups hold and others do not stays as it is (no per-lane branch).  An empty slot
+// contributes phi = -1, no contact and no force, so nothing that is computed changes.  -DRL_SLOT_VALID_ALL: every Spec walks every slot
+// (A/B builds, and the emulator build tests/test_slot_census.py holds the census against).
+template <class SP>
+constexpr uint32_t spec_slot_valid() {
+#ifdef RL_SLOT_VALID_ALL
+  return ~0u;
+#else
+  return SP::SLOT_VALID;
+#endif
+}
+// slot s of some link group in [g_lo, g_hi] holds a sphere
+template <class SP>
+constexpr bool spec_slot_any(int s, int spl, int g_lo, int g_hi) {
+  for (int g = g_lo; g <= g_hi; ++g)
+    if ((spec_slot_valid<SP>() >> (g * spl + s)) & 1u) return true;
+  return false;
+}
 // reward kinds the specialised evaluation implements (a task with any other runs the interpreter: tools/gen_specs.py / robot_lab_amd/jit.py
 // say so).  0 .. 38; not action_mirror (39) / action_sync (40): weight 0 in every shipped cfg.
 constexpr bool spec_kind_supported(int kd) {
@@ -90,6 +113,7 @@ inline bool spec_matches(const TablesT<TopoMax>& T) {
       T.n_bodies != SP::N_BODIES)
     return false;
   if (T.n_rewards != SP::N_REW || T.cur_lin || T.cur_ang) return false;
+  if (T.slot_valid != SP::SLOT_VALID) return false;  // the kernel skips the slots this word leaves empty: a sphere the Spec does not know must not exist
   for (int j = 0; j < SP::TP::CL; ++j)  // a joint the Spec composes in sparse form must be axis-aligned in every limb of THIS env's tables
     for (int k = 0; k < NLANE; ++k)
       if (SP::AXIS_KIND[j] != 3 && table_axis_kind(T.lane[k], j) != SP::AXIS_KIND[j]) return false;

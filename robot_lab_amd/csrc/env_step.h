@@ -912,6 +912,15 @@ struct EnvLane {
   static constexpr bool M0 = TP::M0 != 0;
   static constexpr int G0 = M0 ? 1 : 0;  // first link group of the sub-lane mapping
   RL_FN int grp_of(int it) const { return G0 + sub + SUB * it; }
+  // can sphere slot s hold a sphere in a link group that some owner of iteration `it` has?  A Spec knows its task's slot census
+  // (env_spec.h spec_slot_any); the interpreter walks every slot.  A slot that is not live is not computed, fetched, evaluated or stashed.
+  static constexpr bool slot_live(int it, int s) {
+    const int lo = G0 + SUB * it, hi = lo + SUB - 1 < CL ? lo + SUB - 1 : CL;
+    return spec_slot_any<SP>(s, SPL, lo, hi);
+  }
+  // (the "does this group hold any sphere" word of group_fetch stays the table image's: as a constant of the Spec it saved one LDS read
+  // per kernel and cost the trunk + limbs kernel its scalar register allocation - 358 lane reads more, G1 80.0 -> 80.3 us:
+  // profiles/r07b_ab_slot_word_constant.txt)
   RL_FN bool owns_group(int g) const { return SUB == 1 || (g < G0 ? sub == 0 : ((g - G0) % SUB) == sub); }
   // does the sphere in slot (g, s) ride on the base link instead of limb link g - 1 (merged instances)
   RL_FN bool on_base(int g, int s) const { return M0 && ((L.sph_base_mask >> (g * SPL + s)) & 1u) != 0u; }
@@ -1194,12 +1203,14 @@ struct EnvLane {
     M3 Rg;
     V3 pg;
     group_frame(C, gi, Rg, pg);
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-      sphere_center_in(Rg, pg, Rwb, gi, s, gf.rad[s], gf.cb[s], gf.cw[s]);
-      if (!mine) gf.rad[s] = -1.f;
-      gf.tp[s] = terrain_fetch(u, S.terrain, tb, gf.cw[s].x, gf.cw[s].y);
-    }
+    static_for<0, SPL>([&](auto sc) __attribute__((always_inline)) {
+      constexpr int s = sc.value;
+      if constexpr (slot_live(IT, s)) {
+        sphere_center_in(Rg, pg, Rwb, gi, s, gf.rad[s], gf.cb[s], gf.cw[s]);
+        if (!mine) gf.rad[s] = -1.f;
+        gf.tp[s] = terrain_fetch(u, S.terrain, tb, gf.cw[s].x, gf.cw[s].y);
+      }
+    });
     return true;
   }
 
@@ -1218,11 +1229,16 @@ struct EnvLane {
     float phi[SPL];
     V3 nw[SPL];
     bool touching = false;
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-      patch_phi(gf.tp[s], gf.rad[s], gf.cw[s], phi[s], nw[s]);
-      touching = touching || phi[s] > 0.f;
-    }
+    static_for<0, SPL>([&](auto sc) __attribute__((always_inline)) {
+      constexpr int s = sc.value;
+      if constexpr (slot_live(IT, s)) {
+        patch_phi(gf.tp[s], gf.rad[s], gf.cw[s], phi[s], nw[s]);
+        touching = touching || phi[s] > 0.f;
+      } else {  // what an empty slot evaluates to
+        phi[s] = -1.f;
+        nw[s] = {0.f, 0.f, 0.f};
+      }
+    });
     if (!ctx.any(touching)) return;  // most link groups of most wavefronts touch nothing
     // SPL predicated copies of the contact code (RL_CONTACT_LOOP: every lane walks ITS touching slots instead - the trip count is
     // the maximum over the wavefront of the touching-slot count and the code exists once; measured 3.5 us SLOWER on A1 Rough,
@@ -1300,8 +1316,10 @@ struct EnvLane {
       }
     };
 #ifndef RL_CONTACT_LOOP
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) one_slot(s, gf.rad[s], gf.cb[s], phi[s], nw[s]);
+    static_for<0, SPL>([&](auto sc) __attribute__((always_inline)) {
+      constexpr int s = sc.value;
+      if constexpr (slot_live(IT, s)) one_slot(s, gf.rad[s], gf.cb[s], phi[s], nw[s]);
+    });
 #else
     uint32_t tm = 0;
 #pragma unroll
@@ -2493,8 +2511,9 @@ struct EnvLane {
         if (!ctx.any(bits != 0u)) return;
         Contact c[SPL];
         int slot[SPL];
-#pragma unroll
-        for (int s2 = 0; s2 < SPL; ++s2) {
+        static_for<0, SPL>([&](auto sc) __attribute__((always_inline)) {
+          constexpr int s2 = sc.value;
+          if constexpr (!slot_live(it.value, s2)) return;  // (no contact was stashed there)
           c[s2].act = (bits >> s2) & 1u;
           if constexpr (STASH_REG) {
             const float (&st)[CONTACT_WORDS] = stash_r[it.value * SPL + s2];
@@ -2516,15 +2535,17 @@ struct EnvLane {
             }
           }
           slot[s2] = L.sph_slot[gi][s2];
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < SPL; ++s2)
+        });
+        static_for<0, SPL>([&](auto sc) __attribute__((always_inline)) {
+          constexpr int s2 = sc.value;
+          if constexpr (!slot_live(it.value, s2)) return;
           if (c[s2].act) {
             SV Vs = Vnew[it.value];
             const bool onb = on_base(gi, s2);
             if (M0) Vs = pick_sv(onb, V0n, Vs);
             apply(c[s2], Vs, slot[s2], onb);
           }
+        });
       });
     } else {
       // one lane per limb (RL_ENV_SUB=1 / the CPU emulator's default): no stash - the spheres that were active in pass 1 are

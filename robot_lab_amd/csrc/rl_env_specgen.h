@@ -55,6 +55,7 @@ inline std::string spec_source(const rl_env_desc& d, const char* struct_name, co
   add("struct %s {  // %s\n", struct_name, task);
   add("  static constexpr bool ON = true;\n  static constexpr int ID = %d;\n  static constexpr const char* TASK = \"%s\";\n", id, task);
   add("  using TP = %s;\n  static constexpr int INST = %d, D = %d, N_BODIES = %d, N_REW = %d;\n", topo, inst, T.D, T.n_bodies, T.n_rewards);
+  add("  static constexpr uint32_t SLOT_VALID = 0x%xu;\n", T.slot_valid);  // sphere-slot census (env_spec.h spec_slot_any)
   out += "  static constexpr int JOINT_K[" + std::to_string(T.D) + "] = {";
   for (int i = 0; i < T.D; ++i) out += std::to_string(jk[i]) + (i + 1 < T.D ? ", " : "};\n");
   out += "  static constexpr int JOINT_J[" + std::to_string(T.D) + "] = {";
