@@ -11,8 +11,9 @@
  *
  * y = W_L act(... act(W_1 x + b_1) ...) + b_L in fp32 (exact-f32 MFMA, v_mfma_f32_16x16x4_f32), one kernel launch
  * for the whole network.  All pointers passed to rl_mlp_forward are DEVICE pointers; weights are given once, on the
- * host, in the torch.nn.Linear layout ([out_features][in_features] row-major).  Only inference is provided
- * (no autograd, no rollout storage / GAE - out of scope this round). */
+ * host, in the torch.nn.Linear layout ([out_features][in_features] row-major).  This header is inference only: the
+ * learner (forward + backward + Adam over a stored batch) is include/rl_ppo.h, rollout storage / GAE include/rl_rollout.h;
+ * rl_mlp_set_weights_device is how the learner's parameters reach these kernels without the host. */
 #ifndef RL_POLICY_H
 #define RL_POLICY_H
 
@@ -43,6 +44,12 @@ int rl_mlp_create(const int32_t* dims, int32_t n_layers, int32_t activation, con
  * forward can be reading a half-updated image; the caller must not launch this network from another thread while the call runs.
  * Not capturable: fails (without disturbing the capture) when `stream` is being captured - push parameters between graph replays. */
 int rl_mlp_set_weights(rl_mlp* m, const float* const* weights, const float* const* biases, void* stream);
+
+/* The same in-place update from DEVICE copies of the nn.Linear images (w_dev[l]: [dims[l+1]][dims[l]], b_dev[l]: [dims[l+1]]; the arrays of
+ * pointers themselves are host arrays): the re-layout runs as kernels, stream-ordered on `stream` - no device-wide wait, no host copy,
+ * capturable.  The images keep their addresses and are bit-identical to what rl_mlp_set_weights makes of the same numbers.  Ordering against
+ * forwards on OTHER streams is the caller's (rl_mlp_set_weights waits for the whole device instead). */
+int rl_mlp_set_weights_device(rl_mlp* m, const float* const* w_dev, const float* const* b_dev, void* stream);
 
 /* y[n_rows][dims[n_layers]] = MLP(x[n_rows][dims[0]]); x, y: device pointers, row-major; stream-ordered. */
 int rl_mlp_forward(rl_mlp* m, const float* x_dev, float* y_dev, int32_t n_rows, void* stream);

@@ -1,0 +1,85 @@
+/* rl_ppo.h - C-ABI of the HIP-native PPO learner (csrc/rl_ppo.hip -> librl_ppo_hip.so).
+ *
+ * Replaces `alg.update()` of the reference's training loop (scripts/reinforcement_learning/rsl_rl/train.py:224 -> rsl_rl
+ * `OnPolicyRunner.learn` -> `PPO.update`) for the networks of `.../agents/rsl_rl_ppo_cfg.py` (ELU MLPs, scalar std).  The update
+ * RULE is defined by robot_lab_amd/ppo.py (`PPO.update`); this library evaluates the same rule with hand-written gfx950 kernels:
+ * gathered-row GEMMs in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) for forward, dX and dW, one loss-head kernel,
+ * a fused norm -> clip -> Adam -> floor kernel.  An update only ENQUEUES work on the caller's stream: the KL statistic moves the
+ * learning-rate word on the device, Adam reads it there, the statistics accumulate there.  Every reduction has a fixed order
+ * (no floating-point atomics): the same state and permutation give bit-identical parameters.
+ *
+ * All `*_dev` pointers are DEVICE pointers.  Flat layout (parameters, gradients, Adam moments), the order of
+ * `ActorCritic.parameters()`: std[act], then per actor layer W[out][in], b[out], then the critic's layers alike. */
+#ifndef RL_PPO_H
+#define RL_PPO_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RL_PPO_MAX_LAYERS 8   /* = RL_MLP_MAX_LAYERS */
+#define RL_PPO_MAX_WIDTH 512  /* = RL_MLP_MAX_WIDTH */
+
+enum rl_ppo_activation { RL_PPO_ACT_ELU = 0, RL_PPO_ACT_RELU = 1, RL_PPO_ACT_TANH = 2 }; /* only ELU is implemented; others are refused */
+enum rl_ppo_schedule { RL_PPO_SCHEDULE_FIXED = 0, RL_PPO_SCHEDULE_ADAPTIVE = 1 };
+enum rl_ppo_std_type { RL_PPO_STD_SCALAR = 0, RL_PPO_STD_LOG = 1 }; /* "log" is refused */
+
+typedef struct rl_ppo_hyper {
+  double learning_rate; /* initial; the adaptive schedule keeps it in a device word (fp64, so that /1.5 and x1.5 follow the host learner's path exactly) */
+  double desired_kl;    /* > 0 with the adaptive schedule (refused otherwise; a learner without a KL target is RL_PPO_SCHEDULE_FIXED).
+                           fp64: the thresholds 2 x and / 2 are formed as the host learner forms them */
+  float value_loss_coef, clip_param, entropy_coef, max_grad_norm;
+  int32_t use_clipped_value_loss, num_learning_epochs, num_mini_batches, schedule, std_type;
+} rl_ppo_hyper;
+
+/* the flat [T * N, ...] views of a filled rollout storage (include/rl_rollout.h), fp32 */
+typedef struct rl_ppo_batch {
+  const float *observations, *privileged_observations, *actions; /* [B][obs], [B][critic obs], [B][act] */
+  const float *values, *returns, *advantages, *actions_log_prob; /* [B] */
+  const float *mu, *sigma;                                       /* [B][act] */
+} rl_ppo_batch;
+
+typedef struct rl_ppo rl_ppo;
+
+/* actor_dims / critic_dims: n_layers + 1 widths each (input, hidden..., output); the critic's output width must be 1.  Parameters start at
+ * zero (std at 1): call rl_ppo_set_parameters.  Refused with a reason (rl_ppo_last_error): an activation other than ELU, std_type "log",
+ * widths outside 1..RL_PPO_MAX_WIDTH, more than RL_PPO_MAX_LAYERS layers,
+ * the adaptive schedule without a positive desired_kl.  The arguments are checked before the device is touched. */
+int rl_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation, const rl_ppo_hyper* hyper,
+                  int32_t max_rows_per_minibatch, int32_t device, rl_ppo** out);
+int rl_ppo_destroy(rl_ppo* p);
+const char* rl_ppo_last_error(void);
+
+int64_t rl_ppo_num_parameters(const rl_ppo* p);
+
+/* nn.Linear images ([out][in], [out]) per layer + std[act], device pointers; stream-ordered device-to-device copies.  A null array / pointer
+ * skips that part.  set: also what a loaded checkpoint goes through; get: the way back into an `ActorCritic.state_dict()`. */
+int rl_ppo_set_parameters(rl_ppo* p, const float* const* actor_w_dev, const float* const* actor_b_dev, const float* const* critic_w_dev,
+                          const float* const* critic_b_dev, const float* std_dev, void* stream);
+int rl_ppo_get_parameters(rl_ppo* p, float* const* actor_w_dev, float* const* actor_b_dev, float* const* critic_w_dev, float* const* critic_b_dev,
+                          float* std_dev, void* stream);
+/* the addresses of the master parameters inside the flat buffer (what rl_mlp_set_weights_device reads for a push without the host) */
+int rl_ppo_parameter_pointers(rl_ppo* p, const float** actor_w_dev, const float** actor_b_dev, const float** critic_w_dev, const float** critic_b_dev,
+                              const float** std_dev);
+/* which: 0 parameters, 1 gradients, 2 Adam first moment, 3 Adam second moment -> dst_dev[rl_ppo_num_parameters] */
+int rl_ppo_get_flat(rl_ppo* p, int32_t which, float* dst_dev, void* stream);
+
+/* forward + loss head + backward for the rows idx_dev[0..n_idx) (int64 row numbers into the batch); the gradient of
+ * surrogate + value_loss_coef * value_loss - entropy_coef * entropy (means over the n_idx rows) is left in the flat gradient buffer.
+ * No optimiser step, no change of the learning rate or the statistics of an update. */
+int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream);
+
+/* The whole PPO.update: num_learning_epochs x num_mini_batches mini-batches of n_rows / num_mini_batches rows, mini-batch i of every epoch
+ * taking perm_dev[i * mb .. (i + 1) * mb).  Enqueues only. */
+int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev, int32_t n_rows, void* stream);
+
+/* out[8]: mean value loss, mean surrogate loss, mean entropy, mean KL (0 unless adaptive), learning rate, last pre-clip gradient norm,
+ * mini-batches in the last update, Adam step counter.  Waits for `stream`, one small copy. */
+int rl_ppo_stats(rl_ppo* p, double* out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -207,3 +207,52 @@ class NativeEnv:
             self.close()
         except Exception:
             pass
+
+
+# ---- include/rl_ppo.h: the HIP PPO learner (csrc/rl_ppo.hip -> librl_ppo_hip.so; the host logic is robot_lab_amd/ppo_hip.py) ----------
+PPO_LIB = os.path.join(_HERE, "csrc", "librl_ppo_hip.so")
+PPO_EXPORTS = ["rl_ppo_create", "rl_ppo_destroy", "rl_ppo_last_error", "rl_ppo_num_parameters", "rl_ppo_set_parameters", "rl_ppo_get_parameters",
+               "rl_ppo_parameter_pointers", "rl_ppo_get_flat", "rl_ppo_minibatch_grad", "rl_ppo_update", "rl_ppo_stats"]
+_ppo_lib = None
+
+
+class RlPpoError(RuntimeError):
+    pass
+
+
+class Hyper(C.Structure):
+    """include/rl_ppo.h `rl_ppo_hyper`"""
+    _fields_ = [("learning_rate", C.c_double), ("desired_kl", C.c_double), ("value_loss_coef", C.c_float), ("clip_param", C.c_float),
+                ("entropy_coef", C.c_float), ("max_grad_norm", C.c_float), ("use_clipped_value_loss", C.c_int32), ("num_learning_epochs", C.c_int32),
+                ("num_mini_batches", C.c_int32), ("schedule", C.c_int32), ("std_type", C.c_int32)]
+
+
+class Batch(C.Structure):
+    """include/rl_ppo.h `rl_ppo_batch`"""
+    _fields_ = [(n, C.c_void_p) for n in ("observations", "privileged_observations", "actions", "values", "returns", "advantages", "actions_log_prob", "mu", "sigma")]
+
+
+def load_ppo_library(path: str | None = None) -> C.CDLL:
+    global _ppo_lib
+    path = path or os.environ.get("RL_PPO_LIB") or PPO_LIB  # RL_PPO_LIB: alternative build (kernel ablations)
+    if _ppo_lib is not None and path == PPO_LIB:
+        return _ppo_lib
+    if not os.path.isfile(path):
+        raise RlPpoError(f"{path} not found: run `python -c 'import __graft_entry__ as g; g.build()'` (the HIP learner has no CPU fallback)")
+    lib = C.CDLL(path)
+    pp = C.POINTER(C.c_void_p)
+    lib.rl_ppo_create.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(Hyper), C.c_int32, C.c_int32, pp]
+    lib.rl_ppo_destroy.argtypes = [C.c_void_p]
+    lib.rl_ppo_last_error.restype = C.c_char_p
+    lib.rl_ppo_num_parameters.argtypes = [C.c_void_p]
+    lib.rl_ppo_num_parameters.restype = C.c_int64
+    lib.rl_ppo_set_parameters.argtypes = [C.c_void_p, pp, pp, pp, pp, C.c_void_p, C.c_void_p]
+    lib.rl_ppo_get_parameters.argtypes = [C.c_void_p, pp, pp, pp, pp, C.c_void_p, C.c_void_p]
+    lib.rl_ppo_parameter_pointers.argtypes = [C.c_void_p, pp, pp, pp, pp, pp]
+    lib.rl_ppo_get_flat.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.rl_ppo_minibatch_grad.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.rl_ppo_update.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.rl_ppo_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
+    if path == PPO_LIB:
+        _ppo_lib = lib
+    return lib

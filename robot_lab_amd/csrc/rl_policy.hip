@@ -834,6 +834,29 @@ int upload_layer(rl_mlp* m, int l, const float* weights, const float* biases) {
     return fail("weight upload failed");
   return 0;
 }
+// upload_layer's re-layout from DEVICE copies of the nn.Linear images: every element of the three device images (fp32 fragment image,
+// padded bias, the three bf16 planes) is written by the thread that owns its index, padding included, so the images equal the host path's
+__global__ __launch_bounds__(256) void mlp_repack_kernel(const float* __restrict__ w, const float* __restrict__ bias, int K, int N, int KB, int NT, int KB32, int NTS,
+                                                         float* __restrict__ Wf, float* __restrict__ bp, uint16_t* __restrict__ Wsp) {
+  const size_t nf = (size_t)KB * NT * 256, nb = (size_t)NT * 16, ns = (size_t)KB32 * NTS * 512;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nf + nb + ns; e += (size_t)gridDim.x * 256) {
+    if (e < nf) {
+      const int sI = (int)(e & 3), ln = (int)((e >> 2) & 63), t = (int)((e >> 8) % NT), kb = (int)((e >> 8) / NT);
+      const int k = kb * 16 + 4 * sI + (ln >> 4), n = t * 16 + (ln & 15);
+      Wf[e] = (k < K && n < N) ? w[(size_t)n * K + k] : 0.f;
+    } else if (e < nf + nb) {
+      const size_t n = e - nf;
+      bp[n] = n < (size_t)N ? bias[n] : 0.f;
+    } else {
+      const size_t q = e - nf - nb;
+      const int j = (int)(q & 7), ln = (int)((q >> 3) & 63), t = (int)((q >> 9) % NTS), kb = (int)((q >> 9) / NTS);
+      const int k = kb * 32 + 8 * (ln >> 4) + j, n = t * 16 + (ln & 15);
+      const Split3 sp = (k < K && n < N) ? split3(w[(size_t)n * K + k]) : Split3{0, 0, 0};
+      const size_t o = ((((size_t)kb * NTS + t) * 3) * 64 + ln) * 8 + j;
+      Wsp[o] = sp.h; Wsp[o + 512] = sp.m; Wsp[o + 1024] = sp.l;
+    }
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -854,6 +877,21 @@ int rl_mlp_set_weights(rl_mlp* m, const float* const* weights, const float* cons
   for (int l = 0; l < m->P.n_layers; ++l)
     if (upload_layer(m, l, weights[l], biases[l])) return -1;
   return 0;
+}
+
+int rl_mlp_set_weights_device(rl_mlp* m, const float* const* w_dev, const float* const* b_dev, void* stream) {
+  if (!m || !w_dev || !b_dev) return fail("null argument");
+  for (int l = 0; l < m->P.n_layers; ++l)
+    if (!w_dev[l] || !b_dev[l]) return fail("null layer pointer");
+  if (hipSetDevice(m->device) != hipSuccess) return fail("hipSetDevice failed");
+  for (int l = 0; l < m->P.n_layers; ++l) {
+    const int KB = m->P.KB[l], NT = 8 * m->P.NT8[l], KB32 = m->P.KB32[l], NTS = m->P.NTS[l];
+    const size_t total = (size_t)KB * NT * 256 + (size_t)NT * 16 + (size_t)KB32 * NTS * 512;
+    hipLaunchKernelGGL(mlp_repack_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, (hipStream_t)stream, w_dev[l], b_dev[l],
+                       m->dims[l], m->dims[l + 1], KB, NT, KB32, NTS, const_cast<float*>(m->P.W[l]), const_cast<float*>(m->P.b[l]), const_cast<uint16_t*>(m->P.Ws[l]));
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
 }
 
 int rl_mlp_create(const int32_t* dims, int32_t n_layers, int32_t activation, const float* const* weights, const float* const* biases,

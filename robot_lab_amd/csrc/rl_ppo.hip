@@ -1,0 +1,694 @@
+// rl_ppo.hip - the PPO learner for gfx950 (MI355X): `PPO.update` of robot_lab_amd/ppo.py (rsl_rl's update rule) as HIP kernels.
+// C-ABI: include/rl_ppo.h.
+//
+// One mini-batch is a fixed sequence of launches on the caller's stream, nothing of it returns to the host:
+//   forward   per layer ONE launch for actor and critic (blockIdx.z): Y = elu(X W^T + b), rows of layer 0 gathered through the permutation
+//   head      mean, value + the stored batch -> dL/dmean, dL/dvalue, the per-row terms of dL/dstd, partial loss / KL sums; a one-block
+//             kernel orders the partials, moves the learning-rate word (KL-adaptive schedule) and the Adam step counter
+//   dX        per hidden layer one launch for both networks: dZ_l = (dZ_{l+1} W_l) * elu'(H_l)   (elu' from the stored output: h > 0 ? 1 : h + 1)
+//   dW        ONE launch for every layer of both networks: partial[s] = dZ^T X over the s-th chunk of rows (the deterministic split that
+//             fills the CUs); column sums of dZ (bias gradients, dL/dstd) alike; one reduce launch adds the partials in chunk order
+//   step      sum of squares in fixed blocks -> every block of the Adam kernel adds the same partials in the same order: norm, clip
+//             coefficient, Adam, floor of std
+// The three GEMM shapes are one LDS-tiled kernel (128 x 128 output tile, 16-deep slices, four wavefronts of 64 x 64 = 2 x 2
+// v_mfma_f32_32x32x2_f32 tiles: exact fp32 products, fp32 accumulation in contraction order).
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/rl_ppo.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int TB = 128;       // output tile edge
+constexpr int TK = 16;        // contraction slice
+constexpr int LD = TB + 4;    // LDS row stride: 4 r + i is a distinct bank for the 16 x 4 (r, i) pairs a wavefront stores at once
+constexpr int MAXP = 2 * RL_PPO_MAX_LAYERS + 1;
+constexpr float HALF_LOG_2PI = 0.9189385332046727f;
+
+enum { G_FWD = 0, G_DX = 1, G_DW = 2 };
+
+// C[I][J] = sum_r A(i, r) B(r, j):
+//   G_FWD  i = row, j = output unit, r = input unit:  A = X[row(i)][r],  B = W[j][r];   C = act(. + bias[j])
+//   G_DX   i = row, j = input unit,  r = output unit: A = dZ[i][r],      B = W[r][j];   C = . * elu'(H[i][j])
+//   G_DW   i = output unit, j = input unit, r = row:  A = dZ[r][i],      B = X[row(r)][j]; C = partial[s][i][j] over rows [s chunk, (s + 1) chunk)
+struct GemmProb {
+  const float* A;
+  const float* B;
+  float* C;
+  const float* aux;     // G_FWD: bias; G_DX: H
+  const int64_t* gidx;  // row gather of X (layer 0) or null
+  int I, J, R;
+  int lda, ldb, ldc, ldaux;
+  int tilesJ, ntiles;
+  int act;        // G_FWD: 1 = ELU follows
+  int S, chunk;   // G_DW: number of row chunks, rows per chunk (multiple of TK)
+  long cstride;   // G_DW: floats between the partials of consecutive chunks
+};
+struct GemmBatch {
+  GemmProb p[2 * RL_PPO_MAX_LAYERS];
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
+  const GemmProb& P = batch.p[blockIdx.z];
+  if ((int)blockIdx.x >= P.ntiles || (int)blockIdx.y >= (MODE == G_DW ? P.S : 1)) return;  // (uniform for the workgroup)
+  __shared__ float As[TK * LD];
+  __shared__ float Bs[TK * LD];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int i0 = ((int)blockIdx.x / P.tilesJ) * TB, j0 = ((int)blockIdx.x % P.tilesJ) * TB;
+  const int r_begin = MODE == G_DW ? (int)blockIdx.y * P.chunk : 0;
+  const int r_end = MODE == G_DW ? min(P.R, r_begin + P.chunk) : P.R;
+
+  // a thread's eight elements of either operand tile: contraction-contiguous operands are read 16 r x 16 outer per pass, the others 128 outer x 2 r
+  constexpr bool A_RC = MODE != G_DW, B_RC = MODE == G_FWD;
+  const int a_r = A_RC ? (t & 15) : (t >> 7), a_o = A_RC ? (t >> 4) : (t & 127);
+  const int b_r = B_RC ? (t & 15) : (t >> 7), b_o = B_RC ? (t >> 4) : (t & 127);
+  size_t a_row[8];  // (A_RC) offsets of the eight outer rows
+  size_t b_row[8];
+  if (A_RC) {
+    for (int p = 0; p < 8; ++p) {
+      const int i = i0 + a_o + 16 * p;
+      a_row[p] = i < P.I ? (size_t)(MODE == G_FWD && P.gidx ? P.gidx[i] : i) * P.lda : 0;
+    }
+  }
+  if (B_RC) {
+    for (int p = 0; p < 8; ++p) {
+      const int j = j0 + b_o + 16 * p;
+      b_row[p] = j < P.J ? (size_t)j * P.ldb : 0;
+    }
+  }
+  float ra[8], rb[8];
+  auto fetch = [&](int r0) {
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      if (A_RC) {
+        const int i = i0 + a_o + 16 * p, r = r0 + a_r;
+        ra[p] = (i < P.I && r < r_end) ? P.A[a_row[p] + r] : 0.f;
+      } else {
+        const int i = i0 + a_o, r = r0 + a_r + 2 * p;
+        ra[p] = (i < P.I && r < r_end) ? P.A[(size_t)r * P.lda + i] : 0.f;
+      }
+      if (B_RC) {
+        const int j = j0 + b_o + 16 * p, r = r0 + b_r;
+        rb[p] = (j < P.J && r < r_end) ? P.B[b_row[p] + r] : 0.f;
+      } else {
+        const int j = j0 + b_o, r = r0 + b_r + 2 * p;
+        float v = 0.f;
+        if (j < P.J && r < r_end) {
+          const size_t row = MODE == G_DW && P.gidx ? (size_t)P.gidx[r] : (size_t)r;
+          v = P.B[row * P.ldb + j];
+        }
+        rb[p] = v;
+      }
+    }
+  };
+  auto stash = [&]() {
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      if (A_RC) As[a_r * LD + a_o + 16 * p] = ra[p];
+      else As[(a_r + 2 * p) * LD + a_o] = ra[p];
+      if (B_RC) Bs[b_r * LD + b_o + 16 * p] = rb[p];
+      else Bs[(b_r + 2 * p) * LD + b_o] = rb[p];
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+  const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+  const int lr = lane >> 5, lc = lane & 31;  // MFMA operand maps: A[row = lane & 31][k = lane >> 5], B[k = lane >> 5][col = lane & 31]
+
+  if (r_begin < r_end) fetch(r_begin);
+  for (int r0 = r_begin; r0 < r_end; r0 += TK) {
+    stash();
+    __syncthreads();
+    if (r0 + TK < r_end) fetch(r0 + TK);  // the next slice travels while this one is multiplied
+#pragma unroll
+    for (int kk = 0; kk < TK / 2; ++kk) {
+      const float* ap = As + (2 * kk + lr) * LD + wi + lc;
+      const float* bp = Bs + (2 * kk + lr) * LD + wj + lc;
+      const float a0 = ap[0], a1 = ap[32], b0 = bp[0], b1 = bp[32];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // D map of v_mfma_f32_32x32x2_f32: register 4 g + e holds row 8 g + 4 (lane >> 5) + e, column lane & 31
+  float* C = MODE == G_DW ? P.C + (size_t)blockIdx.y * P.cstride : P.C;
+#pragma unroll
+  for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+      const int j = j0 + wj + 32 * tj + lc;
+      if (j >= P.J) continue;
+      const float bias = MODE == G_FWD ? P.aux[j] : 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = i0 + wi + 32 * ti + 8 * (e >> 2) + 4 * lr + (e & 3);
+        if (i >= P.I) continue;
+        float v = acc[ti][tj][e];
+        if (MODE == G_FWD) {
+          v += bias;
+          if (P.act) v = v > 0.f ? v : expm1f(v);
+        } else if (MODE == G_DX) {
+          const float h = P.aux[(size_t)i * P.ldaux + j];
+          v *= h > 0.f ? 1.f : h + 1.f;
+        }
+        C[(size_t)i * P.ldc + j] = v;
+      }
+    }
+}
+
+// ---- column sums (bias gradients, dL/dstd): part[s][off + n] = sum over the rows of chunk s of Z[m][n], fp64 inside
+struct ColProb {
+  const float* Z;
+  float* part;
+  int N, M, ld, S, chunk;
+  long stride, off;
+};
+struct ColBatch {
+  ColProb p[MAXP];
+};
+__global__ __launch_bounds__(256) void ppo_colsum_kernel(ColBatch batch) {
+  const ColProb& P = batch.p[blockIdx.z];
+  if ((int)blockIdx.y >= P.S || (int)blockIdx.x * 64 >= P.N) return;
+  __shared__ double sh[4][64];
+  const int c = threadIdx.x & 63, q = threadIdx.x >> 6, n = (int)blockIdx.x * 64 + c;
+  const int m0 = (int)blockIdx.y * P.chunk, m1 = min(P.M, m0 + P.chunk);
+  double s = 0.0;
+  if (n < P.N)
+    for (int m = m0 + q; m < m1; m += 4) s += (double)P.Z[(size_t)m * P.ld + n];
+  sh[q][c] = s;
+  __syncthreads();
+  if (q == 0 && n < P.N) P.part[(size_t)blockIdx.y * P.stride + P.off + n] = (float)(((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c]);
+}
+
+// ---- out[i] = sum_s part[s][i], s ascending, fp64 inside
+struct RedProb {
+  const float* part;
+  float* out;
+  long count, stride;
+  int S;
+};
+struct RedBatch {
+  RedProb p[MAXP];
+};
+__global__ __launch_bounds__(256) void ppo_reduce_kernel(RedBatch batch) {
+  const RedProb& P = batch.p[blockIdx.y];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < P.count; i += (long)gridDim.x * 256) {
+    double s = 0.0;
+    for (int k = 0; k < P.S; ++k) s += (double)P.part[(size_t)k * P.stride + i];
+    P.out[i] = (float)s;
+  }
+}
+
+// ---- loss head
+struct DevState {
+  double lr;           // the learning-rate word
+  double acc[4];       // sums over the mini-batches of an update: value loss, surrogate, entropy, KL
+  double grad_norm;    // last pre-clip gradient norm
+  long long step;      // Adam step counter
+  long long n_minibatches;
+};
+struct HeadArgs {
+  const float *mean, *value;  // [n][A], [n]
+  rl_ppo_batch b;
+  const int64_t* idx;
+  const float* std;
+  float *dmean, *dvalue, *dstd_rows;
+  double* partials;  // [blocks][3]: surrogate, value loss, KL sums
+  int n, A;
+  float clip, value_loss_coef, entropy_coef;
+  int use_clipped_value_loss;
+};
+
+__global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
+  __shared__ double sh[3][256];
+  const int m = (int)blockIdx.x * 256 + threadIdx.x;
+  double s_sur = 0.0, s_val = 0.0, s_kl = 0.0;
+  if (m < a.n) {
+    const size_t g = (size_t)a.idx[m];
+    const int A = a.A;
+    const float inv_n = 1.0f / (float)a.n;
+    float logp = 0.f, kl = 0.f;
+    for (int k = 0; k < A; ++k) {
+      const float sd = a.std[k], mu = a.mean[(size_t)m * A + k], d = a.b.actions[g * A + k] - mu;
+      logp += -0.5f * (d * d) / (sd * sd) - logf(sd) - HALF_LOG_2PI;
+      const float so = a.b.sigma[g * A + k], dm = a.b.mu[g * A + k] - mu;
+      kl += logf(sd / so + 1e-5f) + (so * so + dm * dm) / (2.0f * sd * sd) - 0.5f;
+    }
+    const float ratio = expf(logp - a.b.actions_log_prob[g]), adv = a.b.advantages[g];
+    const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
+    const float t1 = -adv * ratio, t2 = -adv * fminf(fmaxf(ratio, lo), hi);
+    const float inr = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
+    // d max(t1, t2) / d ratio as autograd has it: the larger branch; on a tie half of each
+    const float gr = t1 > t2 ? -adv : (t1 < t2 ? -adv * inr : -adv * 0.5f * (1.f + inr));
+    const float c = gr * ratio * inv_n;  // dL / dlogp
+    const float v = a.value[m], ret = a.b.returns[g];
+    float vloss, gv;
+    if (a.use_clipped_value_loss) {
+      const float vo = a.b.values[g], dv = v - vo;
+      const float vc = vo + fminf(fmaxf(dv, -a.clip), a.clip);
+      const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
+      const float in2 = (dv >= -a.clip && dv <= a.clip) ? 1.f : 0.f;
+      const float g1 = 2.f * (v - ret), g2 = 2.f * (vc - ret) * in2;
+      vloss = fmaxf(l1, l2);
+      gv = l1 > l2 ? g1 : (l1 < l2 ? g2 : 0.5f * (g1 + g2));
+    } else {
+      vloss = (ret - v) * (ret - v);
+      gv = 2.f * (v - ret);
+    }
+    a.dvalue[m] = a.value_loss_coef * gv * inv_n;
+    for (int k = 0; k < A; ++k) {
+      const float sd = a.std[k], d = a.b.actions[g * A + k] - a.mean[(size_t)m * A + k];
+      a.dmean[(size_t)m * A + k] = c * d / (sd * sd);
+      // dlogp / dstd and the entropy bonus (-entropy_coef * mean over rows of sum_k log std_k): the column sum over the rows is dL / dstd_k
+      a.dstd_rows[(size_t)m * A + k] = c * (d * d / (sd * sd * sd) - 1.0f / sd) - a.entropy_coef * inv_n / sd;
+    }
+    s_sur = (double)fmaxf(t1, t2);
+    s_val = (double)vloss;
+    s_kl = (double)kl;
+  }
+  sh[0][threadIdx.x] = s_sur; sh[1][threadIdx.x] = s_val; sh[2][threadIdx.x] = s_kl;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) a.partials[(size_t)blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// one workgroup of 64: orders the head's partial sums; with `apply` it books the statistics, moves the learning rate and counts the step
+__global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* partials, int nblocks, int n, const float* std, int A, DevState* st,
+                                                            int apply, int adaptive, double desired_kl) {
+  __shared__ double sh[3][64];
+  for (int q = 0; q < 3; ++q) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 64) s += partials[(size_t)b * 3 + q];
+    sh[q][threadIdx.x] = s;
+  }
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0 || !apply) return;
+  float ent = 0.f;
+  for (int k = 0; k < A; ++k) ent += 0.5f + HALF_LOG_2PI + logf(std[k]);
+  const float kl = (float)(sh[2][0] / (double)n);
+  st->acc[0] += (double)(float)(sh[1][0] / (double)n);
+  st->acc[1] += (double)(float)(sh[0][0] / (double)n);
+  st->acc[2] += (double)ent;
+  if (adaptive) {  // (rl_ppo_create: adaptive implies desired_kl > 0)
+    // the host learner compares an fp32 statistic with thresholds formed in fp64
+    if (kl > (float)(2.0 * desired_kl)) st->lr = fmax(1e-5, st->lr / 1.5);
+    else if (kl > 0.f && kl < (float)(desired_kl / 2.0)) st->lr = fmin(1e-2, st->lr * 1.5);
+    st->acc[3] += (double)kl;
+  }
+  st->step += 1;
+  st->n_minibatches += 1;
+}
+
+// ---- optimiser step
+constexpr int NORM_BLOCKS = 256;
+__global__ __launch_bounds__(256) void ppo_sumsq_kernel(const float* g, long n, double* partial) {
+  __shared__ double sh[256];
+  const long per = (n + NORM_BLOCKS - 1) / NORM_BLOCKS, b0 = (long)blockIdx.x * per, b1 = b0 + per < n ? b0 + per : n;
+  double s = 0.0;
+  for (long i = b0 + threadIdx.x; i < b1; i += 256) s += (double)g[i] * (double)g[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+
+// clip_grad_norm_ (coef = min(1, max_norm / (norm + 1e-6))) + torch.optim.Adam's step (defaults) + the floor of std (the first n_std entries)
+__global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g, float* m1, float* m2, long n, int n_std, const double* partial, DevState* st,
+                                                      float max_norm) {
+  __shared__ double sh[256];
+  sh[threadIdx.x] = partial[threadIdx.x];  // NORM_BLOCKS == blockDim.x; every block adds the same numbers in the same order
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float norm = (float)sqrt(sh[0]);
+  const float coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+  if (blockIdx.x == 0 && threadIdx.x == 0) st->grad_norm = (double)norm;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double step = (double)st->step;
+  const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
+  const float step_size = (float)(st->lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+  const float gi = g[i] * coef;
+  const float m = m1[i] + 0.1f * (gi - m1[i]);                       // exp_avg.lerp_(grad, 1 - beta1)
+  const float v = m2[i] * 0.999f + (float)(1.0 - 0.999) * gi * gi;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+  m1[i] = m;
+  m2[i] = v;
+  const float denom = sqrtf(v) / bc2_sqrt + 1e-8f;
+  float w = p[i] - step_size * (m / denom);
+  if (i < n_std) w = fmaxf(w, 1e-6f);
+  p[i] = w;
+}
+
+std::string& err() {
+  static thread_local std::string e;
+  return e;
+}
+int fail(const std::string& m) {
+  err() = m;
+  return -1;
+}
+
+struct Net {
+  int dims[RL_PPO_MAX_LAYERS + 1] = {};
+  long w_off[RL_PPO_MAX_LAYERS] = {}, b_off[RL_PPO_MAX_LAYERS] = {};  // into the flat buffers
+  float* h[RL_PPO_MAX_LAYERS + 1] = {};   // h[l], l >= 1: output of layer l - 1 ([rows][dims[l]]); h[n_layers]: the network's output
+  float* dz[RL_PPO_MAX_LAYERS + 1] = {};  // dz[l], l >= 1: dL / d(pre-activation of layer l - 1)
+  float* part[RL_PPO_MAX_LAYERS] = {};    // dW / db partials of layer l: [S][N K + N]
+  int S[RL_PPO_MAX_LAYERS] = {};
+};
+
+}  // namespace
+
+struct rl_ppo {
+  int device = 0, L = 0, A = 0, max_rows = 0;
+  rl_ppo_hyper hp{};
+  Net net[2];  // actor, critic
+  long n_params = 0;
+  float *params = nullptr, *grads = nullptr, *m1 = nullptr, *m2 = nullptr;
+  float *dstd_rows = nullptr, *std_part = nullptr;
+  int S_std = 1;
+  double *head_part = nullptr, *norm_part = nullptr;
+  DevState* st = nullptr;
+  std::vector<void*> allocs;
+};
+
+namespace {
+
+template <class T>
+bool dalloc(rl_ppo* p, T** out, size_t count) {
+  void* q = nullptr;
+  if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
+  if (hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
+  p->allocs.push_back(q);
+  *out = (T*)q;
+  return true;
+}
+
+int check_launch() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
+}
+
+int chunk_rows(int n, int S) {  // rows per chunk: a multiple of the GEMM's slice
+  const int c = (n + S - 1) / S;
+  return std::max(TK, (c + TK - 1) / TK * TK);
+}
+
+// the launches of one mini-batch (see the head of this file)
+int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool apply, hipStream_t s) {
+  const int L = p->L;
+  const float* X[2] = {b->observations, b->privileged_observations};
+  for (int l = 0; l < L; ++l) {
+    GemmBatch gb{};
+    int tiles = 0;
+    for (int k = 0; k < 2; ++k) {
+      const Net& N = p->net[k];
+      GemmProb& g = gb.p[k];
+      g.A = l == 0 ? X[k] : N.h[l]; g.gidx = l == 0 ? idx : nullptr; g.lda = N.dims[l];
+      g.B = p->params + N.w_off[l]; g.ldb = N.dims[l];
+      g.aux = p->params + N.b_off[l];
+      g.C = N.h[l + 1]; g.ldc = N.dims[l + 1];
+      g.I = n; g.J = N.dims[l + 1]; g.R = N.dims[l];
+      g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
+      g.act = l + 1 < L;
+      tiles = std::max(tiles, g.ntiles);
+    }
+    hipLaunchKernelGGL(ppo_gemm_kernel<G_FWD>, dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+  }
+  {
+    HeadArgs a{};
+    a.mean = p->net[0].h[L]; a.value = p->net[1].h[L]; a.b = *b; a.idx = idx; a.std = p->params;
+    a.dmean = p->net[0].dz[L]; a.dvalue = p->net[1].dz[L]; a.dstd_rows = p->dstd_rows; a.partials = p->head_part;
+    a.n = n; a.A = p->A; a.clip = p->hp.clip_param; a.value_loss_coef = p->hp.value_loss_coef; a.entropy_coef = p->hp.entropy_coef;
+    a.use_clipped_value_loss = p->hp.use_clipped_value_loss;
+    const int blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(ppo_head_kernel, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, s, p->head_part, blocks, n, p->params, p->A, p->st, apply ? 1 : 0,
+                       p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0, p->hp.desired_kl);
+  }
+  for (int l = L - 1; l >= 1; --l) {
+    GemmBatch gb{};
+    int tiles = 0;
+    for (int k = 0; k < 2; ++k) {
+      const Net& N = p->net[k];
+      GemmProb& g = gb.p[k];
+      g.A = N.dz[l + 1]; g.lda = N.dims[l + 1];
+      g.B = p->params + N.w_off[l]; g.ldb = N.dims[l];
+      g.aux = N.h[l]; g.ldaux = N.dims[l];
+      g.C = N.dz[l]; g.ldc = N.dims[l];
+      g.I = n; g.J = N.dims[l]; g.R = N.dims[l + 1];
+      g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
+      tiles = std::max(tiles, g.ntiles);
+    }
+    hipLaunchKernelGGL(ppo_gemm_kernel<G_DX>, dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+  }
+  {
+    GemmBatch gb{};
+    ColBatch cb{};
+    RedBatch rb{};
+    int tiles = 0, Smax = 1, colx = 1, np = 0;
+    long redmax = 1;
+    for (int k = 0; k < 2; ++k)
+      for (int l = 0; l < L; ++l, ++np) {
+        const Net& N = p->net[k];
+        const int Nn = N.dims[l + 1], K = N.dims[l];
+        GemmProb& g = gb.p[np];
+        g.A = N.dz[l + 1]; g.lda = Nn;
+        g.B = l == 0 ? X[k] : N.h[l]; g.gidx = l == 0 ? idx : nullptr; g.ldb = K;
+        g.C = N.part[l]; g.ldc = K;
+        g.I = Nn; g.J = K; g.R = n;
+        g.tilesJ = (K + TB - 1) / TB; g.ntiles = ((Nn + TB - 1) / TB) * g.tilesJ;
+        g.S = N.S[l]; g.chunk = chunk_rows(n, g.S); g.cstride = (long)Nn * K + Nn;
+        ColProb& c = cb.p[np];
+        c.Z = N.dz[l + 1]; c.part = N.part[l]; c.N = Nn; c.M = n; c.ld = Nn; c.S = g.S; c.chunk = g.chunk; c.stride = g.cstride; c.off = (long)Nn * K;
+        RedProb& r = rb.p[np];
+        r.part = N.part[l]; r.out = p->grads + N.w_off[l]; r.count = g.cstride; r.stride = g.cstride; r.S = g.S;  // (b follows W in the flat layout)
+        tiles = std::max(tiles, g.ntiles); Smax = std::max(Smax, g.S); colx = std::max(colx, (Nn + 63) / 64); redmax = std::max(redmax, r.count);
+      }
+    ColProb& c = cb.p[np];
+    c.Z = p->dstd_rows; c.part = p->std_part; c.N = p->A; c.M = n; c.ld = p->A; c.S = p->S_std; c.chunk = chunk_rows(n, c.S); c.stride = p->A; c.off = 0;
+    RedProb& r = rb.p[np];
+    r.part = p->std_part; r.out = p->grads; r.count = p->A; r.stride = p->A; r.S = p->S_std;
+    colx = std::max(colx, (p->A + 63) / 64); Smax = std::max(Smax, p->S_std);
+    hipLaunchKernelGGL(ppo_gemm_kernel<G_DW>, dim3(tiles, Smax, np), dim3(256), 0, s, gb);
+    hipLaunchKernelGGL(ppo_colsum_kernel, dim3(colx, Smax, np + 1), dim3(256), 0, s, cb);
+    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)std::min<long>((redmax + 255) / 256, 512), np + 1), dim3(256), 0, s, rb);
+  }
+  if (apply) {
+    hipLaunchKernelGGL(ppo_sumsq_kernel, dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part);
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, s, p->params, p->grads, p->m1, p->m2, p->n_params, p->A,
+                       p->norm_part, p->st, p->hp.max_grad_norm);
+  }
+  return check_launch();
+}
+
+int check_batch(const rl_ppo_batch* b) {
+  if (!b || !b->observations || !b->privileged_observations || !b->actions || !b->values || !b->returns || !b->advantages || !b->actions_log_prob ||
+      !b->mu || !b->sigma)
+    return fail("null batch pointer");
+  return 0;
+}
+
+// walks the per-layer images of both networks and std; `to_flat`: user -> flat
+int copy_parameters(rl_ppo* p, const float* const* aw, const float* const* ab, const float* const* cw, const float* const* cb, const float* sd, bool to_flat,
+                    hipStream_t s) {
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  auto cp = [&](const float* user, long off, size_t count) {
+    if (!user) return fail("null layer pointer");
+    float* flat = p->params + off;
+    const hipError_t e = to_flat ? hipMemcpyAsync(flat, user, count * 4, hipMemcpyDeviceToDevice, s)
+                                 : hipMemcpyAsync(const_cast<float*>(user), flat, count * 4, hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
+  };
+  const float* const* W[2] = {aw, cw};
+  const float* const* B[2] = {ab, cb};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < p->L; ++l) {
+      const Net& N = p->net[k];
+      if (W[k] && cp(W[k][l], N.w_off[l], (size_t)N.dims[l] * N.dims[l + 1])) return -1;
+      if (B[k] && cp(B[k][l], N.b_off[l], (size_t)N.dims[l + 1])) return -1;
+    }
+  if (sd && cp(sd, 0, (size_t)p->A)) return -1;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* rl_ppo_last_error(void) { return err().c_str(); }
+
+int rl_ppo_destroy(rl_ppo* p) {
+  if (!p) return 0;
+  (void)hipSetDevice(p->device);
+  for (void* q : p->allocs) (void)hipFree(q);
+  delete p;
+  return 0;
+}
+
+int rl_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation, const rl_ppo_hyper* hyper,
+                  int32_t max_rows_per_minibatch, int32_t device, rl_ppo** out) {
+  if (!actor_dims || !critic_dims || !hyper || !out) return fail("null argument");
+  if (n_layers < 1 || n_layers > RL_PPO_MAX_LAYERS) return fail("unsupported layer count " + std::to_string(n_layers) + " (1.." + std::to_string(RL_PPO_MAX_LAYERS) + ")");
+  if (activation != RL_PPO_ACT_ELU) return fail("unsupported activation: the HIP learner implements ELU only (use the torch learner of robot_lab_amd/ppo.py)");
+  if (hyper->std_type != RL_PPO_STD_SCALAR) return fail("unsupported noise_std_type: the HIP learner implements \"scalar\" only (use the torch learner)");
+  for (int l = 0; l <= n_layers; ++l)
+    if (actor_dims[l] < 1 || actor_dims[l] > RL_PPO_MAX_WIDTH || critic_dims[l] < 1 || critic_dims[l] > RL_PPO_MAX_WIDTH)
+      return fail("unsupported layer width " + std::to_string(std::max(actor_dims[l], critic_dims[l])) + " (1.." + std::to_string(RL_PPO_MAX_WIDTH) + ")");
+  if (critic_dims[n_layers] != 1) return fail("the critic's output width must be 1");
+  if (max_rows_per_minibatch < 1) return fail("max_rows_per_minibatch must be positive");
+  if (hyper->num_learning_epochs < 1 || hyper->num_mini_batches < 1) return fail("num_learning_epochs and num_mini_batches must be positive");
+  if (hyper->schedule != RL_PPO_SCHEDULE_FIXED && hyper->schedule != RL_PPO_SCHEDULE_ADAPTIVE) return fail("unknown schedule");
+  if (hyper->schedule == RL_PPO_SCHEDULE_ADAPTIVE && !(hyper->desired_kl > 0.0))
+    return fail("the adaptive schedule needs desired_kl > 0 (no target: pass RL_PPO_SCHEDULE_FIXED)");
+  if (!(hyper->learning_rate > 0.0) || !(hyper->clip_param > 0.f) || !(hyper->max_grad_norm > 0.f)) return fail("learning_rate, clip_param and max_grad_norm must be positive");
+  if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed (the HIP learner needs a GPU; there is no CPU path)");
+  rl_ppo* p = new rl_ppo();
+  p->device = device; p->L = n_layers; p->A = actor_dims[n_layers]; p->max_rows = max_rows_per_minibatch; p->hp = *hyper;
+  const size_t rows = (size_t)max_rows_per_minibatch;
+  long off = p->A;  // std first: the order of ActorCritic.parameters()
+  for (int k = 0; k < 2; ++k) {
+    Net& N = p->net[k];
+    const int32_t* d = k == 0 ? actor_dims : critic_dims;
+    for (int l = 0; l <= n_layers; ++l) N.dims[l] = d[l];
+    for (int l = 0; l < n_layers; ++l) {
+      N.w_off[l] = off; off += (long)d[l] * d[l + 1];
+      N.b_off[l] = off; off += d[l + 1];
+    }
+  }
+  p->n_params = off;
+  bool ok = dalloc(p, &p->params, (size_t)off) && dalloc(p, &p->grads, (size_t)off) && dalloc(p, &p->m1, (size_t)off) && dalloc(p, &p->m2, (size_t)off);
+  const int s_cap = std::max(1, (max_rows_per_minibatch + TK - 1) / TK);  // no chunk shorter than a slice
+  for (int k = 0; k < 2 && ok; ++k) {
+    Net& N = p->net[k];
+    for (int l = 0; l < n_layers && ok; ++l) {
+      const int Nn = N.dims[l + 1], K = N.dims[l];
+      ok = dalloc(p, &N.h[l + 1], rows * Nn) && dalloc(p, &N.dz[l + 1], rows * Nn);
+      const int tiles = ((Nn + TB - 1) / TB) * ((K + TB - 1) / TB);
+      N.S[l] = std::max(1, std::min(128 / tiles, s_cap));  // ~128 workgroups per layer and network: 1024 in the one dW launch of the A1 networks
+      ok = ok && dalloc(p, &N.part[l], (size_t)N.S[l] * ((size_t)Nn * K + Nn));
+    }
+  }
+  p->S_std = std::max(1, std::min(64, s_cap));
+  ok = ok && dalloc(p, &p->dstd_rows, rows * p->A) && dalloc(p, &p->std_part, (size_t)p->S_std * p->A) &&
+       dalloc(p, &p->head_part, (size_t)((max_rows_per_minibatch + 255) / 256) * 3) && dalloc(p, &p->norm_part, (size_t)NORM_BLOCKS) && dalloc(p, &p->st, 1);
+  if (ok) {
+    std::vector<float> ones((size_t)p->A, 1.0f);
+    DevState st{};
+    st.lr = hyper->learning_rate;
+    ok = hipMemcpy(p->params, ones.data(), ones.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(p->st, &st, sizeof(st), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    rl_ppo_destroy(p);
+    return fail("device allocation failed");
+  }
+  *out = p;
+  return 0;
+}
+
+int64_t rl_ppo_num_parameters(const rl_ppo* p) { return p ? p->n_params : 0; }
+
+int rl_ppo_set_parameters(rl_ppo* p, const float* const* actor_w_dev, const float* const* actor_b_dev, const float* const* critic_w_dev,
+                          const float* const* critic_b_dev, const float* std_dev, void* stream) {
+  if (!p) return fail("null argument");
+  return copy_parameters(p, actor_w_dev, actor_b_dev, critic_w_dev, critic_b_dev, std_dev, true, (hipStream_t)stream);
+}
+
+int rl_ppo_get_parameters(rl_ppo* p, float* const* actor_w_dev, float* const* actor_b_dev, float* const* critic_w_dev, float* const* critic_b_dev,
+                          float* std_dev, void* stream) {
+  if (!p) return fail("null argument");
+  return copy_parameters(p, actor_w_dev, actor_b_dev, critic_w_dev, critic_b_dev, std_dev, false, (hipStream_t)stream);
+}
+
+int rl_ppo_parameter_pointers(rl_ppo* p, const float** actor_w_dev, const float** actor_b_dev, const float** critic_w_dev, const float** critic_b_dev,
+                              const float** std_dev) {
+  if (!p) return fail("null argument");
+  const float** W[2] = {actor_w_dev, critic_w_dev};
+  const float** B[2] = {actor_b_dev, critic_b_dev};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < p->L; ++l) {
+      if (W[k]) W[k][l] = p->params + p->net[k].w_off[l];
+      if (B[k]) B[k][l] = p->params + p->net[k].b_off[l];
+    }
+  if (std_dev) *std_dev = p->params;
+  return 0;
+}
+
+int rl_ppo_get_flat(rl_ppo* p, int32_t which, float* dst_dev, void* stream) {
+  if (!p || !dst_dev) return fail("null argument");
+  if (which < 0 || which > 3) return fail("rl_ppo_get_flat: which must be 0..3");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  const float* src[4] = {p->params, p->grads, p->m1, p->m2};
+  const hipError_t e = hipMemcpyAsync(dst_dev, src[which], (size_t)p->n_params * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
+}
+
+int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream) {
+  if (!p || !idx_dev) return fail("null argument");
+  if (check_batch(batch)) return -1;
+  if (n_idx < 1 || n_idx > p->max_rows) return fail("n_idx outside 1..max_rows_per_minibatch");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  return minibatch(p, batch, idx_dev, n_idx, false, (hipStream_t)stream);
+}
+
+int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev, int32_t n_rows, void* stream) {
+  if (!p || !perm_dev) return fail("null argument");
+  if (check_batch(batch)) return -1;
+  const int mb = n_rows / p->hp.num_mini_batches;
+  if (mb < 1 || mb > p->max_rows) return fail("rows per mini-batch outside 1..max_rows_per_minibatch");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  hipStream_t s = (hipStream_t)stream;
+  // the statistics of THIS update start at zero (stream-ordered: the previous update's are read by rl_ppo_stats before)
+  if (hipMemsetAsync(p->st->acc, 0, sizeof(double) * 4, s) != hipSuccess || hipMemsetAsync(&p->st->n_minibatches, 0, sizeof(long long), s) != hipSuccess)
+    return fail("cannot reset the statistics block");
+  for (int e = 0; e < p->hp.num_learning_epochs; ++e)
+    for (int i = 0; i < p->hp.num_mini_batches; ++i)
+      if (minibatch(p, batch, perm_dev + (size_t)i * mb, mb, true, s)) return -1;
+  return 0;
+}
+
+int rl_ppo_stats(rl_ppo* p, double* out, void* stream) {
+  if (!p || !out) return fail("null argument");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("stream synchronisation failed");
+  DevState st{};
+  if (hipMemcpy(&st, p->st, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return fail("statistics copy failed");
+  const double n = st.n_minibatches > 0 ? (double)st.n_minibatches : 1.0;
+  out[0] = st.acc[0] / n; out[1] = st.acc[1] / n; out[2] = st.acc[2] / n; out[3] = st.acc[3] / n;
+  out[4] = st.lr; out[5] = st.grad_norm; out[6] = (double)st.n_minibatches; out[7] = (double)st.step;
+  return 0;
+}
+
+}  // extern "C"

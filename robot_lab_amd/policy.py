@@ -16,7 +16,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 POLICY_LIB = os.path.join(_HERE, "csrc", "librl_policy_hip.so")
-POLICY_EXPORTS = ["rl_mlp_create", "rl_mlp_set_weights", "rl_mlp_forward", "rl_mlp_forward_small", "rl_mlp_forward_pair", "rl_mlp_forward_pair_act", "rl_mlp_in_dim", "rl_mlp_out_dim", "rl_mlp_destroy", "rl_mlp_last_error"]
+POLICY_EXPORTS = ["rl_mlp_create", "rl_mlp_set_weights", "rl_mlp_set_weights_device", "rl_mlp_forward", "rl_mlp_forward_small", "rl_mlp_forward_pair", "rl_mlp_forward_pair_act", "rl_mlp_in_dim", "rl_mlp_out_dim", "rl_mlp_destroy", "rl_mlp_last_error"]
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2}
 _lib = None
 
@@ -36,6 +36,7 @@ def load_policy_library(path: str | None = None) -> C.CDLL:
     fpp = C.POINTER(C.POINTER(C.c_float))
     lib.rl_mlp_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.c_int32, fpp, fpp, C.c_int32, C.POINTER(C.c_void_p)]
     lib.rl_mlp_set_weights.argtypes = [C.c_void_p, fpp, fpp, C.c_void_p]
+    lib.rl_mlp_set_weights_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
     lib.rl_mlp_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rl_mlp_forward_small.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rl_mlp_forward_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -96,6 +97,26 @@ class MlpPolicy:
         bp = (fp * n)(*[b.ctypes.data_as(fp) for b in bs])
         stream = self._torch.cuda.current_stream(self.device).cuda_stream
         if self.lib.rl_mlp_set_weights(self.handle, wp, bp, C.c_void_p(stream)) != 0:
+            raise RlPolicyError((self.lib.rl_mlp_last_error() or b"").decode())
+
+    def set_weights_device(self, weights, biases):
+        """`set_weights` from float32 DEVICE tensors (or raw device addresses) without the host (`rl_mlp_set_weights_device`): the re-layout is a
+        kernel on the current stream - no device-wide wait, capturable.  The caller keeps the tensors alive until the stream has passed it."""
+        n = len(self._shapes)
+        if len(weights) != n or len(biases) != n:
+            raise ValueError("set_weights_device: layer count differs from the network's")
+
+        def addr(t, shape):
+            if isinstance(t, int):
+                return t
+            if tuple(t.shape) != tuple(shape) or t.dtype != self._torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"set_weights_device: expected a contiguous float32 tensor {tuple(shape)} on {self.device}")
+            return t.data_ptr()
+
+        wp = (C.c_void_p * n)(*[addr(w, s) for w, s in zip(weights, self._shapes)])
+        bp = (C.c_void_p * n)(*[addr(b, (s[0],)) for b, s in zip(biases, self._shapes)])
+        stream = self._torch.cuda.current_stream(self.device).cuda_stream
+        if self.lib.rl_mlp_set_weights_device(self.handle, wp, bp, C.c_void_p(stream)) != 0:
             raise RlPolicyError((self.lib.rl_mlp_last_error() or b"").decode())
 
     def load_linear_layers(self, module):

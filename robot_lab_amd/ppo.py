@@ -133,10 +133,12 @@ class PPO:
 
 
 class Trainer:
-    """collect (HIP, one graph launch) -> update (torch) -> push parameters, repeated: `OnPolicyRunner.learn` in miniature."""
+    """collect (HIP, one graph launch) -> update -> push parameters, repeated: `OnPolicyRunner.learn` in miniature.
+    `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (single GPU),
+    pushed into the inference kernels device to device; `state_dict()` is rsl_rl's layout with either."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
-                 critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, **ppo_kw):
+                 critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", **ppo_kw):
         from .collect import Collector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
@@ -146,7 +148,15 @@ class Trainer:
         torch.manual_seed(seed)
         self.env, self.device = env, obs["policy"].device
         self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std).to(self.device)
-        self.alg = PPO(self.policy, group=group, **ppo_kw)
+        if learner not in ("torch", "hip"):
+            raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
+        self.learner = learner
+        if learner == "hip":
+            from .ppo_hip import HipPPO
+
+            self.alg = HipPPO(self.policy, group=group, max_rows_per_minibatch=max(1, num_steps_per_env * env.num_envs // ppo_kw.get("num_mini_batches", 4)), **ppo_kw)
+        else:
+            self.alg = PPO(self.policy, group=group, **ppo_kw)
         if group is not None:
             group.broadcast_parameters(self.policy)  # before the inference images are built from them
         lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
@@ -159,7 +169,23 @@ class Trainer:
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self.iteration = 0
 
+    def __repr__(self):
+        return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration})"
+
+    def state_dict(self):
+        """rsl_rl's `ActorCritic.state_dict()` layout; the HIP learner's master parameters are copied back into the module first."""
+        if self.learner == "hip":
+            self.alg.store_into(self.policy)
+        return self.policy.state_dict()
+
     def push_parameters(self):
+        if self.learner == "hip":
+            # Device to device on the CURRENT stream, with no device-wide wait (unlike rl_mlp_set_weights below).  Ordering relied on: the update
+            # ran on this stream, so the push follows it; the next collection - eager or the captured graph - is launched on this same stream, so
+            # it follows the push; with Collector(overlap=True) the critic's side stream waits for this stream at the head of every step
+            # (collect.py: side.wait_stream(main)), in the capture too.  A collector launched from ANOTHER stream would have to wait for this one.
+            self.alg.push(self.actor, self.critic, self.std)
+            return
         self.actor.load_linear_layers(self.policy.actor)
         self.critic.load_linear_layers(self.policy.critic)
         self.std.copy_(self.policy.std.detach().clamp_min(1e-6))
@@ -170,6 +196,6 @@ class Trainer:
         out = dict(mean_reward=float(st.rewards.mean()), done_rate=float(st.dones.float().mean()))
         out.update(self.alg.update(st, self.gen))
         self.push_parameters()
-        out["action_std"] = float(self.policy.std.detach().mean())
+        out["action_std"] = float((self.std if self.learner == "hip" else self.policy.std.detach()).mean())
         self.iteration += 1
         return out

@@ -1,0 +1,247 @@
+"""The HIP-native PPO learner (`include/rl_ppo.h`, `csrc/rl_ppo.hip`): `PPO.update` of `robot_lab_amd/ppo.py` without torch autograd.
+
+`ppo.PPO` stays the DEFINITION of the update rule (and the multi-GPU learner); `HipPPO` evaluates the same rule - clipped surrogate,
+clipped value loss, entropy bonus, KL-adaptive learning rate, gradient-norm clipping, Adam, the floor of std - with hand-written
+gfx950 kernels on fp32 master parameters that live on the device.  One `update()` enqueues `num_learning_epochs x num_mini_batches`
+mini-batches on the current stream and reads ONE small statistics block afterwards: no host synchronisation and no host decision
+inside the update (the learning rate is a device word).  Opt-in: `Trainer(env, learner="hip")`, `tools/train_demo.py --learner hip`.
+
+    alg = HipPPO(policy)                 # same keywords as ppo.PPO; copies the ActorCritic's parameters to the device (`load_from`)
+    stats = alg.update(storage, gen)     # same statistics keys as PPO.update; draws the permutation as PPO.update does
+    alg.push(actor, critic, std)         # new parameters into the inference kernels, device to device (rl_mlp_set_weights_device)
+    alg.store_into(policy)               # back into the ActorCritic (checkpoints keep rsl_rl's state_dict layout)
+
+There is no CPU path and no fall-back to the torch learner: a missing library or an unsupported network raises."""
+from __future__ import annotations
+
+import ctypes as C
+
+from .capi import PPO_EXPORTS, PPO_LIB, Batch, Hyper, RlPpoError, load_ppo_library  # noqa: F401  (the binding of include/rl_ppo.h)
+
+ACTIVATIONS = {"ELU": 0, "ReLU": 1, "Tanh": 2}
+MAX_LAYERS, MAX_WIDTH = 8, 512
+
+
+def _network(seq, name):
+    """(dims, activation class name) of an nn.Sequential of Linear layers with one activation between them; anything else is refused."""
+    from torch import nn
+
+    mods = list(seq)
+    lin = [m for m in mods if isinstance(m, nn.Linear)]
+    acts = [m for m in mods if not isinstance(m, nn.Linear)]
+    if not lin or len(mods) != 2 * len(lin) - 1 or any(isinstance(m, nn.Linear) != (i % 2 == 0) for i, m in enumerate(mods)):
+        raise ValueError(f"HipPPO: the {name} is not a Linear / activation / ... / Linear stack: unsupported network (use the torch learner, ppo.PPO)")
+    kinds = {type(m).__name__ for m in acts}
+    if len(kinds) > 1:
+        raise ValueError(f"HipPPO: the {name} mixes activations {sorted(kinds)}: unsupported network (use the torch learner, ppo.PPO)")
+    if any(m.bias is None for m in lin):
+        raise ValueError(f"HipPPO: the {name} has a Linear layer without bias: unsupported network (use the torch learner, ppo.PPO)")
+    return [lin[0].in_features] + [m.out_features for m in lin], (kinds.pop() if kinds else "ELU")
+
+
+class HipPPO:
+    """`ppo.PPO` on the HIP learner: same constructor keywords, same `update(storage, generator) -> dict`."""
+
+    def __init__(self, policy, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01, num_learning_epochs=5,
+                 num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0, group=None,
+                 max_rows_per_minibatch=None, lib_path: str | None = None):
+        import torch
+
+        if group is not None:
+            raise NotImplementedError("HipPPO is a single-GPU learner: the multi-GPU path (gradient all-reduce over a LearnerGroup) is the torch learner, "
+                                      "robot_lab_amd.ppo.PPO (Trainer(..., learner=\"torch\", group=...))")
+        if schedule not in ("adaptive", "fixed"):
+            raise ValueError(f"HipPPO: unknown schedule {schedule!r} (\"adaptive\" or \"fixed\")")
+        self._torch = torch
+        self.handle = None
+        adims, aact = _network(policy.actor, "actor")
+        cdims, cact = _network(policy.critic, "critic")
+        std = getattr(policy, "std", None)
+        if std is None or getattr(policy, "noise_std_type", "scalar") != "scalar":
+            raise ValueError("HipPPO: noise_std_type=\"log\" (or a policy without a `std` parameter) is unsupported: the HIP learner implements the scalar std only")
+        if len(adims) != len(cdims):
+            raise ValueError(f"HipPPO: actor and critic differ in depth ({len(adims) - 1} / {len(cdims) - 1} layers): unsupported network (use the torch learner)")
+        if aact != cact or aact != "ELU":
+            raise ValueError(f"HipPPO: unsupported activation {aact} / {cact}: the HIP learner implements ELU only (use the torch learner, ppo.PPO)")
+        if len(adims) - 1 > MAX_LAYERS or max(adims + cdims) > MAX_WIDTH:
+            raise ValueError(f"HipPPO: unsupported network: at most {MAX_LAYERS} layers of width <= {MAX_WIDTH} (got actor {adims}, critic {cdims}); use the torch learner")
+        if tuple(std.shape) != (adims[-1],):
+            raise ValueError("HipPPO: std must have one entry per action")
+        if desired_kl is not None and not desired_kl > 0:
+            raise ValueError(f"HipPPO: desired_kl={desired_kl!r} is unsupported: a positive target, or None for no KL-adaptive learning rate")
+        if std.device.type != "cuda" or any(p.device != std.device for p in policy.parameters()):
+            raise ValueError(f"HipPPO: the policy must live on one CUDA device (std is on {std.device}): the HIP learner has no CPU path - "
+                             "move it with policy.to(\"cuda:0\") or use the torch learner, ppo.PPO")
+        self.lib = load_ppo_library(lib_path)
+        self.actor_dims, self.critic_dims, self.n_layers = adims, cdims, len(adims) - 1
+        self.value_loss_coef, self.use_clipped_value_loss, self.clip_param, self.entropy_coef = value_loss_coef, use_clipped_value_loss, clip_param, entropy_coef
+        self.num_learning_epochs, self.num_mini_batches = num_learning_epochs, num_mini_batches
+        self.learning_rate, self.schedule, self.desired_kl, self.max_grad_norm = learning_rate, schedule, desired_kl, max_grad_norm
+        self.group = None
+        self.device = std.device
+        self.max_rows = int(max_rows_per_minibatch or 0)
+        self._policy = policy
+        self.last_grad_norm = float("nan")
+        if self.max_rows:
+            self._create(self.max_rows)
+
+    # -- handle ---------------------------------------------------------------------------------------------------------------------
+    def _hyper(self):
+        return Hyper(learning_rate=float(self.learning_rate), desired_kl=float(self.desired_kl) if self.desired_kl is not None else 0.0,
+                     value_loss_coef=self.value_loss_coef, clip_param=self.clip_param, entropy_coef=self.entropy_coef, max_grad_norm=self.max_grad_norm,
+                     use_clipped_value_loss=int(bool(self.use_clipped_value_loss)), num_learning_epochs=self.num_learning_epochs,
+                     num_mini_batches=self.num_mini_batches,
+                     schedule=1 if self.schedule == "adaptive" and self.desired_kl is not None else 0, std_type=0)  # (ppo.py: adaptive needs a target)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RlPpoError((self.lib.rl_ppo_last_error() or b"").decode())
+
+    def _create(self, max_rows):
+        """(the handle is sized by the largest mini-batch: created at the first update unless `max_rows_per_minibatch` was given)"""
+        hp, n = self._hyper(), self.n_layers
+        handle = C.c_void_p()
+        rc = self.lib.rl_ppo_create((C.c_int32 * (n + 1))(*self.actor_dims), (C.c_int32 * (n + 1))(*self.critic_dims), n, ACTIVATIONS["ELU"], C.byref(hp),
+                                    int(max_rows), self.device.index or 0, C.byref(handle))
+        self._check(rc)
+        self.handle, self.max_rows = handle, int(max_rows)
+        self.num_parameters = int(self.lib.rl_ppo_num_parameters(self.handle))
+        if self._policy is not None:
+            self.load_from(self._policy)
+            self._policy = None
+
+    def _need(self, rows):
+        if self.handle is None:
+            self._create(rows)
+        elif rows > self.max_rows:
+            raise RlPpoError(f"mini-batch of {rows} rows > max_rows_per_minibatch {self.max_rows} the learner was created with")
+
+    def _stream(self):
+        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _layers(self, policy):
+        nn = self._torch.nn
+        la, lc = [m for m in policy.actor if isinstance(m, nn.Linear)], [m for m in policy.critic if isinstance(m, nn.Linear)]
+        if [la[0].in_features] + [m.out_features for m in la] != self.actor_dims or [lc[0].in_features] + [m.out_features for m in lc] != self.critic_dims:
+            raise ValueError("HipPPO: the policy's layer shapes differ from the learner's")
+        return la, lc
+
+    def _arrays(self, policy):
+        la, lc = self._layers(policy)
+        ts = []
+
+        def arr(params):
+            out = []
+            for t in params:
+                t = t.detach()
+                if t.dtype != self._torch.float32 or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"HipPPO: parameters must be contiguous float32 tensors on {self.device}")
+                ts.append(t)
+                out.append(t.data_ptr())
+            return (C.c_void_p * len(out))(*out)
+
+        return arr(m.weight for m in la), arr(m.bias for m in la), arr(m.weight for m in lc), arr(m.bias for m in lc), policy.std.detach()
+
+    def load_from(self, policy):
+        """The ActorCritic's parameters become the learner's master parameters (device-to-device).  Adam's moments and step are kept."""
+        if self.handle is None:
+            self._policy = policy
+            return
+        aw, ab, cw, cb, std = self._arrays(policy)
+        self._check(self.lib.rl_ppo_set_parameters(self.handle, aw, ab, cw, cb, C.c_void_p(std.data_ptr()), self._stream()))
+
+    def store_into(self, policy):
+        """The master parameters back into an ActorCritic (for `state_dict()`: rsl_rl's checkpoint layout)."""
+        if self.handle is None:
+            if self._policy is not None and self._policy is not policy:
+                policy.load_state_dict(self._policy.state_dict())
+            return policy
+        aw, ab, cw, cb, std = self._arrays(policy)
+        self._check(self.lib.rl_ppo_get_parameters(self.handle, aw, ab, cw, cb, C.c_void_p(std.data_ptr()), self._stream()))
+        return policy
+
+    def push(self, actor, critic, std_tensor):
+        """The master parameters into the inference kernels' images (`MlpPolicy`) and the sampling kernel's std tensor, on the current
+        stream, without the host: `rl_mlp_set_weights_device` reads the flat parameter buffer in place."""
+        if self.handle is None:
+            raise RlPpoError("HipPPO.push before the first update: nothing to push")
+        n = self.n_layers
+        aw, ab, cw, cb = ((C.c_void_p * n)() for _ in range(4))
+        sd = C.c_void_p()
+        self._check(self.lib.rl_ppo_parameter_pointers(self.handle, aw, ab, cw, cb, C.byref(sd)))
+        actor.set_weights_device([int(x) for x in aw], [int(x) for x in ab])
+        critic.set_weights_device([int(x) for x in cw], [int(x) for x in cb])
+        if std_tensor.dtype != self._torch.float32 or not std_tensor.is_contiguous() or std_tensor.numel() != self.actor_dims[-1]:
+            raise ValueError("HipPPO.push: std_tensor must be a contiguous float32 tensor with one entry per action")
+        self._check(self.lib.rl_ppo_get_parameters(self.handle, None, None, None, None, C.c_void_p(std_tensor.data_ptr()), self._stream()))
+
+    def flat(self, which="parameters"):
+        """A copy of a flat device buffer (`ActorCritic.parameters()` order): "parameters", "gradients", "exp_avg", "exp_avg_sq"."""
+        if self.handle is None:
+            raise RlPpoError("HipPPO.flat before the handle exists (pass max_rows_per_minibatch or run an update)")
+        out = self._torch.empty(self.num_parameters, device=self.device, dtype=self._torch.float32)
+        self._check(self.lib.rl_ppo_get_flat(self.handle, ["parameters", "gradients", "exp_avg", "exp_avg_sq"].index(which), C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    # -- the update -----------------------------------------------------------------------------------------------------------------
+    def _batch(self, storage):
+        torch = self._torch
+        T, N = storage.num_transitions_per_env, storage.num_envs
+        keep = []
+
+        def ptr(t, width):
+            t = t.reshape(T * N, -1)
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                t = t.to(device=self.device, dtype=torch.float32).contiguous()
+            if t.shape[1] != width:
+                raise ValueError(f"HipPPO: storage tensor of width {t.shape[1]}, expected {width}")
+            keep.append(t)
+            return t.data_ptr()
+
+        A = self.actor_dims[-1]
+        b = Batch(observations=ptr(storage.observations, self.actor_dims[0]), privileged_observations=ptr(storage.privileged_observations, self.critic_dims[0]),
+                  actions=ptr(storage.actions, A), values=ptr(storage.values, 1), returns=ptr(storage.returns, 1), advantages=ptr(storage.advantages, 1),
+                  actions_log_prob=ptr(storage.actions_log_prob, 1), mu=ptr(storage.mu, A), sigma=ptr(storage.sigma, A))
+        return b, keep, T * N
+
+    def minibatch_grad(self, storage, idx):
+        """Forward, loss head and backward on the rows `idx` (int64 device tensor); returns the flat gradient.  No optimiser step."""
+        b, keep, T_N = self._batch(storage)
+        idx = idx.to(device=self.device, dtype=self._torch.int64).contiguous()
+        if idx.numel() < 1 or int(idx.min()) < 0 or int(idx.max()) >= T_N:
+            raise ValueError("HipPPO.minibatch_grad: idx must hold row numbers of the batch")
+        self._need(idx.numel())
+        self._check(self.lib.rl_ppo_minibatch_grad(self.handle, C.byref(b), C.c_void_p(idx.data_ptr()), idx.numel(), self._stream()))
+        return self.flat("gradients")
+
+    def update(self, storage, generator=None, perm=None) -> dict:
+        """`PPO.update`: one permutation per update (drawn as `PPO.update` draws it unless `perm` is given), walked once per epoch."""
+        torch = self._torch
+        b, keep, B = self._batch(storage)
+        if perm is None:
+            perm = torch.randperm(B, device=self.device, generator=generator)
+        else:  # the caller's rows (a test stepping one mini-batch at a time): checked, they index device memory
+            if perm.numel() < self.num_mini_batches or perm.numel() > B or int(perm.min()) < 0 or int(perm.max()) >= B:
+                raise ValueError("HipPPO.update: perm must hold between num_mini_batches and T * N row numbers of the batch")
+        perm = perm.to(device=self.device, dtype=torch.int64).contiguous()
+        rows = perm.numel()
+        self._need(rows // self.num_mini_batches)
+        self._check(self.lib.rl_ppo_update(self.handle, C.byref(b), C.c_void_p(perm.data_ptr()), rows, self._stream()))
+        out = (C.c_double * 8)()
+        self._check(self.lib.rl_ppo_stats(self.handle, out, self._stream()))  # the one wait of the update (keeps `keep` / `perm` alive until then)
+        self.learning_rate, self.last_grad_norm = float(out[4]), float(out[5])
+        return dict(value_loss=float(out[0]), surrogate_loss=float(out[1]), entropy=float(out[2]), kl=float(out[3]), learning_rate=self.learning_rate)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.rl_ppo_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def __repr__(self):
+        return f"HipPPO(actor={self.actor_dims}, critic={self.critic_dims}, schedule={self.schedule!r}, lr={self.learning_rate:g}, librl_ppo_hip)"

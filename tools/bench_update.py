@@ -1,0 +1,83 @@
+#!/usr/bin/env python
+"""Time of one PPO update (5 epochs x 4 mini-batches) on ONE collected batch, both learners from the same process on the same box:
+
+    torch: robot_lab_amd/ppo.py `PPO.update` (autograd, the update rule's definition)
+    hip:   robot_lab_amd/ppo_hip.py `HipPPO.update` (csrc/rl_ppo.hip)
+
+The batch is collected once by the HIP collector with a freshly initialised policy; then the two learners are timed ALTERNATELY
+(torch, hip, torch, hip, ...) with device events around each `update()` - which ends in the learner's own read-back of the statistics, so
+the host-side cost of each learner is inside its window - after `--warmup` untimed updates of each.  Reported per learner: median,
+min, max over `--repeat` updates, in ms; and the algorithmic FLOPs of an update (forward + dX + dW of both networks, computed from
+the shapes) over the median.  One JSON line per task.
+    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W]"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from robot_lab_amd.env import ManagerBasedRLEnv  # noqa: E402
+from robot_lab_amd.ppo import PPO, Trainer  # noqa: E402
+from robot_lab_amd.ppo_hip import HipPPO  # noqa: E402
+
+
+def update_flops(alg: HipPPO, rows: int) -> float:
+    """2 flops per multiply-add x (forward + dW for every layer, dX for every layer but the first) x rows x epochs"""
+    macs = 0
+    for dims in (alg.actor_dims, alg.critic_dims):
+        for l in range(len(dims) - 1):
+            macs += dims[l] * dims[l + 1] * (3 if l > 0 else 2)
+    return 2.0 * macs * rows * alg.num_learning_epochs
+
+
+def bench(task, num_envs, repeat, warmup, seed=42):
+    env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
+    tr = Trainer(env, seed=seed)
+    tr.collector.collect()
+    torch.cuda.synchronize()
+    st = tr.storage
+    learners = {"torch": PPO(copy.deepcopy(tr.policy)), "hip": HipPPO(copy.deepcopy(tr.policy))}
+    gens = {k: torch.Generator(device="cuda:0").manual_seed(seed) for k in learners}
+    times = {k: [] for k in learners}
+    for it in range(warmup + repeat):
+        for k, alg in learners.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            out = alg.update(st, gens[k])
+            t1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                times[k].append(t0.elapsed_time(t1))
+            assert all(v == v for v in out.values()), (k, out)  # no NaN
+    rows = st.num_transitions_per_env * st.num_envs
+    flops = update_flops(learners["hip"], rows)
+    res = dict(task=task, num_envs=num_envs, rows=rows, repeat=repeat, warmup=warmup, update_gflop=flops / 1e9)
+    for k, t in times.items():
+        med = statistics.median(t)
+        res[k] = dict(median_ms=med, min_ms=min(t), max_ms=max(t), tflops_at_median=flops / med / 1e9)
+    res["speedup_median"] = res["torch"]["median_ms"] / res["hip"]["median_ms"]
+    learners["hip"].close()
+    env.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--task", nargs="+", default=["RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0", "RobotLab-Isaac-Velocity-Rough-Unitree-G1-v0"])
+    ap.add_argument("--num-envs", nargs="+", type=int, default=[4096, 2048])
+    ap.add_argument("--repeat", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    if len(a.num_envs) != len(a.task):
+        ap.error("one --num-envs per --task")
+    for task, n in zip(a.task, a.num_envs):
+        print(json.dumps(bench(task, n, a.repeat, a.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
