@@ -27,11 +27,6 @@
 //                     [wavefront][id] behind the reward-term rows (tools/phase_clock.py reads them): s_waitcnt 0, read the clock,
 //                     add the interval to the phase that ends, read the clock again - the bookkeeping itself is not counted.
 // The ids index tools/phase_clock.py PHASES.
-// RL_PK: the joint elimination and the contact blocks on packed fp32 pairs (rl_math.h F2p; eliminate_pk below).  On by default - one call,
-// specialised kernels: A1 33.95 -> 33.61 us, G1 86.19 -> 84.65 (profiles/r06m_a1_pk_ab.txt, r06m_g1_pk_ab.txt); -DRL_NO_PK: the scalar form.
-#if !defined(RL_NO_PK) && !defined(RL_PK)
-#define RL_PK 1
-#endif
 #if defined(RL_PHASE_MARKS) && defined(__HIP_DEVICE_COMPILE__)
 #define RL_PHASE(id, name) asm volatile("; PHASE " name)
 #elif defined(RL_PHASE_CLOCK) && defined(__HIP_DEVICE_COMPILE__)
@@ -120,28 +115,10 @@ RL_FN F2 ld2(const float* p) {  // 4-byte aligned 8-byte load
   return {p[0], p[1]};
 #endif
 }
-// The heightfield in HBM: the caller's row-major grid.  -DRL_TERRAIN_PAIRS (analysis switch; rl_env_host.h builds the array): rows ix and
-// ix + 1 interleaved, hf2[(ix * ny + iy) * 2 + {0, 1}] = {h(ix, iy), h(ix + 1, iy)}, so that the four corners of cell (ix, iy) are FOUR
-// CONSECUTIVE WORDS - one 16-byte load and 1.25 cache lines per query instead of two 8-byte loads in two rows 16 KB apart (2.1 lines), at
-// twice the grid's bytes.  Measured in one call and NOT kept: A1 32.57 / 32.62 us, Go2W 38.82 / 38.62, G1 82.27 / 82.28
-// (profiles/r06s_*_hf2_ab.txt) - the lookups are batched loads whose latency is covered either way; their line count is not what the step waits for.
-#ifdef RL_TERRAIN_PAIRS
-constexpr bool TERRAIN_PAIRS = true;
-#else
-constexpr bool TERRAIN_PAIRS = false;
-#endif
-struct F4h {
-  float x, y, z, w;
-};
-RL_FN F4h ld4_a8(const float* p) {  // 8-byte aligned 16-byte load
-#if defined(__HIP_DEVICE_COMPILE__)
-  typedef float f4v __attribute__((ext_vector_type(4), aligned(8)));
-  f4v v = *reinterpret_cast<const f4v*>(p);
-  return {v.x, v.y, v.z, v.w};
-#else
-  return {p[0], p[1], p[2], p[3]};
-#endif
-}
+// The heightfield in HBM: the caller's row-major grid.  (Tried: rows ix and ix + 1 interleaved, so that the four corners of a cell are one
+// 16-byte load and 1.25 cache lines instead of two 8-byte loads in two rows 16 KB apart, at twice the grid's bytes.  No gain - A1 32.57 /
+// 32.62 us, Go2W 38.82 / 38.62, G1 82.27 / 82.28, profiles/r06s_*_hf2_ab.txt: the lookups are batched loads whose latency is covered
+// either way; their line count is not what the step waits for.)
 struct TerrainPatch {
   float h00, h01, h10, h11, fx, fy;
 };
@@ -190,14 +167,10 @@ RL_FN TerrainPatch terrain_fetch(const Uni& u, const float* __restrict__ hf, con
   // arithmetic above meaningless - (int)NaN is 0, (float)(-cx) rounds - and an unclamped cell index then reads far outside the
   // heightfield (a GPU memory fault took the whole launch down on a model with a zero velocity limit, profiles/r03p_all_tasks.txt)
   const int ix = imin(imax(tb.cx + (int)ox, 0), u.nx - 2), iy = imin(imax(tb.cy + (int)oy, 0), u.ny - 2);
-  if constexpr (TERRAIN_PAIRS) {  // {h(ix, iy), h(ix + 1, iy), h(ix, iy + 1), h(ix + 1, iy + 1)}: one load
-    const F4h r = ld4_a8(hf + (((uint32_t)ix * (uint32_t)u.ny + (uint32_t)iy) << 1));
-    p.h00 = r.x; p.h10 = r.y; p.h01 = r.z; p.h11 = r.w;
-  } else {  // (iy, iy+1) are adjacent in memory: two 8-byte loads per query instead of four 4-byte ones
-    const float* b = hf + (uint32_t)ix * (uint32_t)u.ny + (uint32_t)iy;
-    F2 r0 = ld2(b), r1 = ld2(b + u.ny);
-    p.h00 = r0.x; p.h01 = r0.y; p.h10 = r1.x; p.h11 = r1.y;
-  }
+  // (iy, iy+1) are adjacent in memory: two 8-byte loads per query instead of four 4-byte ones
+  const float* b = hf + (uint32_t)ix * (uint32_t)u.ny + (uint32_t)iy;
+  F2 r0 = ld2(b), r1 = ld2(b + u.ny);
+  p.h00 = r0.x; p.h01 = r0.y; p.h10 = r1.x; p.h11 = r1.y;
   return p;
 }
 RL_FN TerrainPatch terrain_fetch(const Uni& u, const float* __restrict__ hf, float bx, float by, float dx, float dy) {
@@ -442,7 +415,8 @@ RL_FN void trunk_frame_of_pose(const LT& L, const float (&q)[TP::JX], uint32_t r
 // they are DEALT: joint jx is computed by sub-lane jx % SUB only, and when the chain product reaches joint jx every sub-lane takes
 // T_jx from its owner with nine quad broadcasts.  What stays per lane and joint is R_j = R_parent * T_j, the joint origin and the
 // world axis (axis_w = R_j * axis: Rodrigues(axis, .) leaves its own axis where it is, so this equals rot-frame * axis).  About
-// 60 instead of 110 instructions per joint of the 10-joint chain, five times per step.
+// 60 instead of 110 instructions per joint of the 10-joint chain, five times per step: G1 148.0 -> 144.9 us against every sub-lane
+// computing every joint transform (profiles/r03x_g1_dealt_kinematics_ab.txt).
 // (SUB here is the DEALING width: the sub-lanes of a DPP quad - with eight sub-lanes per limb each of the limb's two quads deals among
 // its own four lanes, `sub` = the lane's index in its quad, and the broadcasts stay single quad_perm moves: Ctx::deal_bcast_m3.)
 template <class TP, int SUB, class Ctx, class CT, class FT = NoJoint, class FL = NoJoint>
@@ -561,19 +535,12 @@ struct LsMat {
 // accumulator per trunk link (base, waist links, torso) that the limbs and the trunk links' owners ds_add into, and 8 words per
 // self-collision capsule (centre, half axis, radius, bounding radius in base coordinates: EnvLane::self_place).
 constexpr int LINK_REC = 27;  // 21 (6 x 6 symmetric) + 6
-// How a link record sits in LDS.  Default: the packed upper triangle + rho as seven 16-byte vectors, every sub-lane of a limb eliminating
-// the whole record.  -DRL_ELIM_ROWS: six rows of 8 words [A[r][0..5], rho_r, 0] - the FULL matrix - so that the sub-lanes of a DPP quad
-// can each take rows of it (distributed elimination, EnvLane::eliminate_rows).  Measured in one call (profiles/r04h_elim_ab.txt): 1.2 k
-// fewer vector instructions per step and 20 more LDS words per record buy nothing - G1 107.5 against 107.7 us, GR1T1 126.4 against
-// 125.8 us: the elimination is a latency chain (reciprocal, quad sums and broadcasts per joint), not an issue-bound block.  Kept as an
-// analysis switch.
-#ifdef RL_ELIM_ROWS
-constexpr bool REC_ROWS = true;
-constexpr int REC_STRIDE = 48;
-#else
-constexpr bool REC_ROWS = false;
+// How a link record sits in LDS: the packed upper triangle + rho as seven 16-byte vectors, every sub-lane of a limb eliminating the whole
+// record.  (Tried: six rows of 8 words - the FULL matrix, 48 words a record - so that the four sub-lanes of a DPP quad each eliminate one or
+// two rows of a joint's 6 x 6 work, D and u as quad sums, U / D gathered with six quad broadcasts.  1.2 k fewer vector instructions per step
+// and nothing gained - G1 107.5 against 107.7 us, GR1T1 126.4 against 125.8, profiles/r04h_elim_ab.txt: the elimination is a latency chain
+// (reciprocal, quad sums and broadcasts per joint), not an issue-bound block.)
 constexpr int REC_STRIDE = 28;
-#endif
 // a limb's block padded to 4 (mod 32) words: the blocks of the 8 / 16 limbs of a wavefront then start in different banks (b32: 32 banks,
 // b128: 64), so that the same word of every limb - what a wavefront instruction touches - is conflict free
 constexpr int pad_limb_block(int w) { return ((w - 4 + 31) / 32) * 32 + 4; }
@@ -602,12 +569,9 @@ struct LsFor {  // lane scratchpad layout of an instance
   // every contact of pass 1 is kept for the sensor pass (slot it * SPL + s): in the lane scratchpad - or, with eight sub-lanes per limb
   // (ONE link group per sub-lane: 4 slots x 9 words), in REGISTERS: 9.2 KB of LDS per wavefront less, which is what lets four
   // wavefronts of the six-joint-spine instance (GR1) share a CU (2048 envs: 236 -> one round), and 72 scratchpad instructions per
-  // touching lane and substep
-#ifdef RL_STASH_REG_QUAD  // (A/B switch: the 16-lane quadruped kernels keep their 3-slot stash in registers as well)
-  static constexpr bool STASH_REG = SUB == 8 || (SUB == 4 && TP::NW == 0);
-#else
+  // touching lane and substep.  (The 16-lane quadruped kernels keep their 3-slot stash in LDS: in registers A1 42.72 -> 42.92 us,
+  // profiles/r04g_a1_stash_ab.txt.)
   static constexpr bool STASH_REG = SUB == 8;
-#endif
   static constexpr int STASH = (SUB > 1 && !STASH_REG) ? NIT * TP::SPL : 0;
   static constexpr int NOWN = SUB == 1 ? 0 : LaneTabT<TP>::template maxown<SUB>();  // 16- / 8-lane mappings: rows for the owned slots only
   static constexpr bool GRAN = SUB != 1;  // 16-byte granules (see LsMat)
@@ -646,12 +610,10 @@ struct EnvLane {
       kinematics_scan<false>(C, z, z, s0, s1, s2);
       return;
     }
-#ifndef RL_KIN_REPLICATED  // (A/B switch: every sub-lane computes every joint transform)
     if constexpr (NW > 0 && SUB > 1) {
       chain_kinematics_dealt<TP, (SUB < 4 ? SUB : 4)>(ctx, SUB > 4 ? (sub & 3) : sub, L, q, C, u.trunk_restart, on_trunk, on_limb);
       return;
     }
-#endif
     chain_kinematics<TP, SP>(L, q, C, u.trunk_restart, on_trunk, on_limb);
   }
   RL_FN ChainTP new_chain() const { return ChainTP(LDSU ? ctx.limb_chain() : nullptr); }
@@ -665,12 +627,9 @@ struct EnvLane {
   // S_i qd_i and bias accelerations a_j = a_attach + sum_{i <= j} V_i x S_i qd_i are two prefix SUMS of six words (VEL).  The trunk joints
   // (shared by all limbs) stay a chain in every lane, their local transforms dealt over the lane's DPP quad as before.
   // Products and sums associate as a tree here and left to right there: round-off apart (the parity tiers' tolerances), not bits.
-  // Readers of another lane's words need the wave-local fence (ctx.group_sync) first.
-#ifdef RL_KIN_DEALT  // (A/B switch: the dealt chain of round 4)
-  static constexpr bool KIN_SCAN = false;
-#else
+  // Readers of another lane's words need the wave-local fence (ctx.group_sync) first.  Against the dealt chain: G1 94.87 -> 89.29 us, GR1T1
+  // 114.2 -> 109.5 (profiles/r05u_kin_scan_ab.txt).
   static constexpr bool KIN_SCAN = NW > 0 && SUB == 8 && CL <= 8;
-#endif
   template <bool VEL>
   RL_FN void kinematics_scan(ChainTP& C, const SV V0, const SV a0, SV (&Sw)[NW > 0 ? NW : 1], SV (&Vw)[NW > 0 ? NW : 1], SV (&aw)[NW > 0 ? NW : 1]) {
     static_assert(NW > 0 && SUB == 8, "trunk + limbs instance, eight sub-lanes per limb");
@@ -804,11 +763,7 @@ struct EnvLane {
   //    substep loop and spilled them: 260 B of scratch.  Buffers: no scratch, 44 fewer registers, 108.4 -> 97.6 us at 16384 envs.
   //    (The other mappings LOSE with buffers - A1 42.7 -> 50.5 us, G1 107.4 -> 127.6 us: buffer loads are not hoisted, every substep
   //    re-reads its constants from HBM on the critical path of a lone wavefront.)
-#ifdef RL_STATE_BUF_ALL  // buffers in every mapping (A/B)
-  static constexpr bool STATE_BUF = true;
-#else
   static constexpr bool STATE_BUF = SUB == 1;
-#endif
   float* lt;  // this leg's column of the wave tile:   field f -> lt[f * ROW]
   float* et;  // this env's column of the env tile:    field f -> et[f * EPT]
   typename Ctx::StateBuf lt_b, et_b;  // the wavefront's lane-state / env-state tile
@@ -1180,13 +1135,9 @@ struct EnvLane {
     float A[B6::size];  // 6 x 6 symmetric, [omega; v] order
     float r[6];
   };
-#ifdef RL_PK_CONTACT_ALL  // (A/B switches: the contact blocks on packed pairs in every instance / in none)
-  static constexpr bool PK_CONTACT = true;
-#elif defined(RL_NO_PK_CONTACT)
-  static constexpr bool PK_CONTACT = false;
-#else
+  // the contact blocks on packed fp32 pairs (add_to in group_contacts): G1 83.41 -> 82.94 us with them; the quadrupeds lose - A1 33.06 -> 33.24,
+  // register copies eat the saving where a lane has three sphere slots - and keep them scalar (profiles/r06o_*_pk_contact_ab.txt)
   static constexpr bool PK_CONTACT = NW > 0;
-#endif
   struct GroupFetch {
     float rad[SPL];
     V3 cb[SPL], cw[SPL];
@@ -1240,9 +1191,9 @@ struct EnvLane {
       }
     });
     if (!ctx.any(touching)) return;  // most link groups of most wavefronts touch nothing
-    // SPL predicated copies of the contact code (RL_CONTACT_LOOP: every lane walks ITS touching slots instead - the trip count is
-    // the maximum over the wavefront of the touching-slot count and the code exists once; measured 3.5 us SLOWER on A1 Rough,
-    // 56.6 vs 53.0 us in one gpurun call: the select chain per trip and the ballot per trip cost more than the skipped copies)
+    // SPL predicated copies of the contact code.  (Tried: a loop in which every lane walks ITS touching slots - the trip count the maximum
+    // over the wavefront of the touching-slot count, the code existing once.  3.5 us SLOWER on A1 Rough, 56.6 against 53.0 us in one call: the
+    // select chain and the ballot per trip cost more than the skipped copies.)
     auto one_slot = [&](const int s, const float rad_s, const V3 cb_s, const float phi_s, const V3 nw_s) __attribute__((always_inline)) {
       const bool onb = M0 && on_base(gi, s);
       SV Vs = Vg;
@@ -1281,9 +1232,9 @@ struct EnvLane {
         b6[B6::at(2, 3)] = -kt * x.y; b6[B6::at(2, 4)] = kt * x.x;
         b6[B6::at(3, 3)] = kt; b6[B6::at(4, 4)] = kt; b6[B6::at(5, 5)] = kt;
         auto add_to = [&](LinkRec& d) __attribute__((always_inline)) {
-#ifdef RL_PK  // the same sums pair by pair (eliminate_pk has the pairing of the packed triangle): d.A += b + (kn g) g^T, d.r += fb g
-          // (not the merged instances: their two call sites - base share or link - are tail-merged into one body behind a SELECTED record
-          // address, and both records leave the registers: 208 - 544 B of private memory per lane, the build's gate)
+          // the trunk + limbs instances: the same sums pair by pair (eliminate_pk has the pairing of the packed triangle): d.A += b + (kn g) g^T,
+          // d.r += fb g.  (Not the merged instances: their two call sites - base share or link - are tail-merged into one body behind a SELECTED
+          // record address, and both records leave the registers: 208 - 544 B of private memory per lane, the build's gate.)
           if constexpr (!M0 && PK_CONTACT) {
           const F2p g01 = pk2(g6[0], g6[1]), g23 = pk2(g6[2], g6[3]), g45 = pk2(g6[4], g6[5]);
           const F2p k01 = pk_mul(pk1(kn), g01), k23 = pk_mul(pk1(kn), g23), k45 = pk_mul(pk1(kn), g45);
@@ -1302,7 +1253,6 @@ struct EnvLane {
           d.r[0] = r01.x; d.r[1] = r01.y; d.r[2] = r23.x; d.r[3] = r23.y; d.r[4] = r45.x; d.r[5] = r45.y;
           return;
           }
-#endif
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
             d.r[i] += fb * g6[i];
@@ -1315,26 +1265,10 @@ struct EnvLane {
         else add_to(acc);
       }
     };
-#ifndef RL_CONTACT_LOOP
     static_for<0, SPL>([&](auto sc) __attribute__((always_inline)) {
       constexpr int s = sc.value;
       if constexpr (slot_live(IT, s)) one_slot(s, gf.rad[s], gf.cb[s], phi[s], nw[s]);
     });
-#else
-    uint32_t tm = 0;
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) tm |= phi[s] > 0.f ? (1u << s) : 0u;
-#pragma unroll 1
-    for (; ctx.any(tm != 0u); tm &= tm - 1u) {
-      const int s = tm != 0u ? __builtin_ctz(tm) : 0;
-      float rad_s = gf.rad[0], phi_s = tm != 0u ? phi[0] : -1.f;
-      V3 cb_s = gf.cb[0], nw_s = nw[0];
-#pragma unroll
-      for (int i = 1; i < SPL; ++i)
-        if (s == i) { rad_s = gf.rad[i]; phi_s = tm != 0u ? phi[i] : -1.f; cb_s = gf.cb[i]; nw_s = nw[i]; }
-      one_slot(s, rad_s, cb_s, phi_s, nw_s);
-    }
-#endif
   }
 
   // rec += rigid spatial inertia (base coordinates) and rho = h - dt f of a body with inertia I moving with V under the bias
@@ -1407,12 +1341,9 @@ struct EnvLane {
   // are computed right after substep s has moved the joints, its sphere centres follow and the heightfield loads are issued -
   // they fly (L2 / MALL: 300 - 900 cycles) while the sensor timers, the actuators and the rigid link records are worked on.
   // quadrupeds, 16 lanes per env: sub-lane s of a limb also owns limb joint s's actuator and joint-local terms (actuators_owned: three or
-  // four joints on four sub-lanes) - what the trunk + limbs instances do with eight.  -DRL_ACT_REPLICATED: every sub-lane every joint (A/B)
-#ifdef RL_ACT_REPLICATED
-  static constexpr bool ACT_OWNED = false;
-#else
+  // four joints on four sub-lanes) - what the trunk + limbs instances do with eight.  Against every sub-lane evaluating every joint: A1 35.45 ->
+  // 35.03 us, Go2W 43.08 -> 41.10 (profiles/r05aa_quad_act_owned_ab.txt)
   static constexpr bool ACT_OWNED = NW == 0 && SUB == 4 && CL <= 4;
-#endif
   RL_FN void substeps_aba(const float (&q_tgt)[JX], const float (&qd_tgt)[JX], int n) {
     const uint32_t slot_valid = (uint32_t)ctx.uniform_i((int)T.slot_valid);
     ChainTP C = new_chain();
@@ -1454,6 +1385,8 @@ struct EnvLane {
   // as packed fp32 arithmetic (rl_math.h F2p): U = A s - every pair once down its columns, (U_c, U_c+1) += (A_rc, A_rc+1) s_r, and once
   // along its row, U_r += (A_rc, A_rc+1) . (s_c, s_c+1); D = d + s . U and u = t + s . rho as three pairs each; the rank-1 update pair by pair.
   // ~58 instead of 82 vector instructions per joint on paper, ~65 as compiled (a pair is an even-aligned register pair: some copies remain).
+  // Against the scalar loops (U = A s row by row, the rank-1 update entry by entry), one call, specialised kernels: A1 33.95 -> 33.61 us,
+  // G1 86.19 -> 84.65 (profiles/r06m_a1_pk_ab.txt, r06m_g1_pk_ab.txt).
   RL_FN static void eliminate_pk(float (&A)[B6::size], float (&rho)[6], const float (&s)[6], float D0, float u0, float (&Uh)[6], float& ui) {
     const F2p s23 = pk2(s[2], s[3]), s45 = pk2(s[4], s[5]);
     F2p u01 = pk_mul(pk2(A[0], A[1]), pk1(s[0]));
@@ -1577,30 +1510,7 @@ struct EnvLane {
         if (TP::PAD) D += j >= L.nj ? 1.0f : 0.f;  // an inert padding joint (zero axis, no gains): the identity row, as joint_terms() of the trunk + limbs instances
         uu = arm * qd[j] + dt * tau_e[j] + pd_rhs[j] + dt * u.limit_k * viol;
       }
-#ifdef RL_PK
       eliminate_pk(P.A, P.r, s6, D, uu, Uh[j], ui[j]);
-#else
-      float U6[6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        float t = 0.f;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) t += P.A[B6::at(r, c)] * s6[c];
-        U6[r] = t;
-        D += s6[r] * t;
-        uu += s6[r] * P.r[r];
-      }
-      const float inv = frcp(D);
-      ui[j] = uu * inv;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) Uh[j][r] = U6[r] * inv;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        P.r[r] -= U6[r] * ui[j];
-#pragma unroll
-        for (int c = r; c < 6; ++c) P.A[B6::at(r, c)] -= U6[r] * Uh[j][c];
-      }
-#endif
     });
     // the lane's share of the base link's contacts (group 0, owned by sub-lane 0 in iteration 0), when anybody has one
     if (M0) {  // flagged slots of any sub-lane
@@ -1696,161 +1606,51 @@ struct EnvLane {
   RL_FN float* rec_words(int g) const { return ctx.limb_rec() + LB_REC + (g - 1) * REC_STRIDE; }  // link group g = limb link g - 1 (1 .. CL)
   RL_FN float* va_words(int j) const { return ctx.limb_rec() + LB_VA + j * 12; }
   RL_FN float* trunk_words(int d) const { return ctx.env_scratch() + d * REC_STRIDE; }
-  // a link record <-> LDS (REC_ROWS: six rows of [A[r][0..5], rho_r, 0]; else seven vectors of the packed upper triangle + rho)
+  // a link record <-> LDS: seven vectors of the packed upper triangle + rho in the order of rec_pos_A / rec_pos_r - every 8-byte half is
+  // one pair of the packed arithmetic
   RL_FN static void st_rec(float* w, const LinkRec& r) {
-    if constexpr (REC_ROWS) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        st4(w + 8 * q, F4{r.A[B6::at(q, 0)], r.A[B6::at(q, 1)], r.A[B6::at(q, 2)], r.A[B6::at(q, 3)]});
-        st4(w + 8 * q + 4, F4{r.A[B6::at(q, 4)], r.A[B6::at(q, 5)], r.r[q], 0.f});
-      }
-    } else {  // seven vectors in the order of rec_pos_A / rec_pos_r: every 8-byte half is one pair of the packed arithmetic
-      st4(w, F4{r.A[0], r.A[1], r.A[2], r.A[3]});
-      st4(w + 4, F4{r.A[4], r.A[5], r.A[7], r.A[8]});
-      st4(w + 8, F4{r.A[9], r.A[10], r.A[11], r.A[12]});
-      st4(w + 12, F4{r.A[13], r.A[14], r.A[16], r.A[17]});
-      st4(w + 16, F4{r.A[18], r.A[19], r.A[6], r.A[15]});
-      st4(w + 20, F4{r.r[0], r.r[1], r.r[2], r.r[3]});
-      st4(w + 24, F4{r.r[4], r.r[5], r.A[20], 0.f});
-    }
+    st4(w, F4{r.A[0], r.A[1], r.A[2], r.A[3]});
+    st4(w + 4, F4{r.A[4], r.A[5], r.A[7], r.A[8]});
+    st4(w + 8, F4{r.A[9], r.A[10], r.A[11], r.A[12]});
+    st4(w + 12, F4{r.A[13], r.A[14], r.A[16], r.A[17]});
+    st4(w + 16, F4{r.A[18], r.A[19], r.A[6], r.A[15]});
+    st4(w + 20, F4{r.r[0], r.r[1], r.r[2], r.r[3]});
+    st4(w + 24, F4{r.r[4], r.r[5], r.A[20], 0.f});
   }
   // word of a packed record in LDS that holds entry i of the upper triangle / rho_r: the pairs eliminate_pk works on - (0,1) (2,3) (4,5)
   // (7,8) (9,10) (11,12) (13,14) (16,17) (18,19), rho (0,1) (2,3) (4,5) - are the 8-byte halves of the record's 16-byte vectors, so
-  // that add_rec is 13 packed additions on the loaded register pairs as they are (+ the three lone diagonal entries 6, 15, 20)
+  // that acc_rec is 13 packed additions on the loaded register pairs as they are (+ the three lone diagonal entries 6, 15, 20)
   static constexpr int rec_pos_A(int i) { return i <= 5 ? i : i == 6 ? 18 : i <= 14 ? i - 1 : i == 15 ? 19 : i <= 19 ? i - 2 : 26; }
   static constexpr int rec_pos_r(int r) { return 20 + r; }
-  RL_FN static void add_rec(const float* w, LinkRec& P) {  // (the replicated elimination: the whole record into every lane)
-    if constexpr (REC_ROWS) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const F4 a = ld4(w + 8 * q), c = ld4(w + 8 * q + 4);
-        const float row[6] = {a.x, a.y, a.z, a.w, c.x, c.y};
-#pragma unroll
-        for (int cc = q; cc < 6; ++cc) P.A[B6::at(q, cc)] += row[cc];
-        P.r[q] += c.z;
-      }
-    } else {
-      F4 v[7];
-      ld_rec(w, v);
-      acc_rec(v, P);
-    }
-  }
-  // the two halves of add_rec for the packed layout: the record's seven vectors into registers / onto P (the limb elimination issues
-  // the loads of the NEXT joint's record before it eliminates the current one - substep_aba_trunk)
-#ifdef RL_NO_REC_PREFETCH
-  static constexpr bool REC_PREFETCH = false;
-#else
-  static constexpr bool REC_PREFETCH = !REC_ROWS;
-#endif
+  // P += the record at w in two halves: its seven vectors into registers (ld_rec) and onto P (acc_rec) - the limb elimination issues the
+  // loads of the NEXT joint's record before it eliminates the current one (substep_aba_trunk)
   RL_FN static void ld_rec(const float* w, F4 (&v)[7]) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) v[i] = ld4(w + 4 * i);
   }
   RL_FN static void acc_rec(const F4 (&v)[7], LinkRec& P) {
-    {
-      auto acc = [&](float& a, float& b, float x, float y) __attribute__((always_inline)) {
-#ifdef RL_PK
-        const F2p t = pk_add(pk2(a, b), pk2(x, y));
-        a = t.x; b = t.y;
-#else
-        a += x; b += y;
-#endif
-      };
-      acc(P.A[0], P.A[1], v[0].x, v[0].y); acc(P.A[2], P.A[3], v[0].z, v[0].w);
-      acc(P.A[4], P.A[5], v[1].x, v[1].y); acc(P.A[7], P.A[8], v[1].z, v[1].w);
-      acc(P.A[9], P.A[10], v[2].x, v[2].y); acc(P.A[11], P.A[12], v[2].z, v[2].w);
-      acc(P.A[13], P.A[14], v[3].x, v[3].y); acc(P.A[16], P.A[17], v[3].z, v[3].w);
-      acc(P.A[18], P.A[19], v[4].x, v[4].y);
-      P.A[6] += v[4].z; P.A[15] += v[4].w;
-      acc(P.r[0], P.r[1], v[5].x, v[5].y); acc(P.r[2], P.r[3], v[5].z, v[5].w);
-      acc(P.r[4], P.r[5], v[6].x, v[6].y);
-      P.A[20] += v[6].z;
-    }
+    auto acc = [&](float& a, float& b, float x, float y) __attribute__((always_inline)) {
+      const F2p t = pk_add(pk2(a, b), pk2(x, y));
+      a = t.x; b = t.y;
+    };
+    acc(P.A[0], P.A[1], v[0].x, v[0].y); acc(P.A[2], P.A[3], v[0].z, v[0].w);
+    acc(P.A[4], P.A[5], v[1].x, v[1].y); acc(P.A[7], P.A[8], v[1].z, v[1].w);
+    acc(P.A[9], P.A[10], v[2].x, v[2].y); acc(P.A[11], P.A[12], v[2].z, v[2].w);
+    acc(P.A[13], P.A[14], v[3].x, v[3].y); acc(P.A[16], P.A[17], v[3].z, v[3].w);
+    acc(P.A[18], P.A[19], v[4].x, v[4].y);
+    P.A[6] += v[4].z; P.A[15] += v[4].w;
+    acc(P.r[0], P.r[1], v[5].x, v[5].y); acc(P.r[2], P.r[3], v[5].z, v[5].w);
+    acc(P.r[4], P.r[5], v[6].x, v[6].y);
+    P.A[20] += v[6].z;
   }
-  RL_FN static float* rho_word(float* w, int r) { return REC_ROWS ? w + 8 * r + 6 : w + rec_pos_r(r); }  // rho_r of a record at w
+  RL_FN static float* rho_word(float* w, int r) { return w + rec_pos_r(r); }  // rho_r of a record at w
   RL_FN static void atomic_add_rec(float* w, const LinkRec& r) {  // ds_add_f32 of a whole record (several lanes of an env add into one)
-    if constexpr (REC_ROWS) {
 #pragma unroll
-      for (int q = 0; q < 6; ++q) {
+    for (int i = 0; i < B6::size; ++i) Ctx::limb_atomic_add(w + rec_pos_A(i), r.A[i]);
 #pragma unroll
-        for (int c = 0; c < 6; ++c) Ctx::limb_atomic_add(w + 8 * q + c, r.A[B6::at(q, c)]);
-        Ctx::limb_atomic_add(w + 8 * q + 6, r.r[q]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < B6::size; ++i) Ctx::limb_atomic_add(w + rec_pos_A(i), r.A[i]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) Ctx::limb_atomic_add(w + rec_pos_r(i), r.r[i]);
-    }
+    for (int i = 0; i < 6; ++i) Ctx::limb_atomic_add(w + rec_pos_r(i), r.r[i]);
   }
 
-  // ---- DISTRIBUTED elimination (trunk + limbs instances, SUB >= 4): the four lanes of a DPP quad hold identical copies of everything the
-  // limb recursion needs, so they SHARE a joint's 6 x 6 work by rows instead of each repeating it: quad lane q carries row q of the
-  // articulated inertia (and row q + 4 where q < 2; the other two lanes a zero phantom row) and its rho entries.  Per joint: the lane's
-  // one or two rows of the link record from LDS (2 - 4 vectors instead of 7), U_r = P_r . s (12 FMA instead of 36), D and u as two quad
-  // sums, U / D gathered into every lane with six quad broadcasts, the rank-1 update of the lane's rows (14 FMA instead of 27).
-  // ~60 vector instructions per joint instead of ~140; same linear system, the sums in tree order.
-  static constexpr bool ELIM_DIST = REC_ROWS && SUB >= 4 && NW > 0;
-  struct Rows {
-    float a[6], ra, b[6], rb;
-  };
-  RL_FN static void rows_zero(Rows& P) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) P.a[c] = P.b[c] = 0.f;
-    P.ra = P.rb = 0.f;
-  }
-  RL_FN void rows_add(const float* w, Rows& P) const {
-    const int q = sub & 3, rb = q < 2 ? q + 4 : 5;
-    const float wb = q < 2 ? 1.f : 0.f;
-    const F4 a0 = ld4(w + 8 * q), a1 = ld4(w + 8 * q + 4), b0 = ld4(w + 8 * rb), b1 = ld4(w + 8 * rb + 4);
-    P.a[0] += a0.x; P.a[1] += a0.y; P.a[2] += a0.z; P.a[3] += a0.w; P.a[4] += a1.x; P.a[5] += a1.y; P.ra += a1.z;
-    P.b[0] += wb * b0.x; P.b[1] += wb * b0.y; P.b[2] += wb * b0.z; P.b[3] += wb * b0.w; P.b[4] += wb * b1.x; P.b[5] += wb * b1.y; P.rb += wb * b1.z;
-  }
-  RL_FN static void rows_acc(Rows& P, const Rows& Q) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) { P.a[c] += Q.a[c]; P.b[c] += Q.b[c]; }
-    P.ra += Q.ra; P.rb += Q.rb;
-  }
-  RL_FN void eliminate_rows(Rows& P, const float (&s6)[6], float D0, float u0, float (&Uh)[6], float& ui) const {
-    const int q = sub & 3;
-    float Ua = 0.f, Ub = 0.f;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) { Ua += P.a[c] * s6[c]; Ub += P.b[c] * s6[c]; }
-    // the lane's own entries of s: a 0/1-weighted sum (a select chain on q is lowered to a jump table of exec-masked blocks)
-    const float e0 = q == 0 ? 1.f : 0.f, e1 = q == 1 ? 1.f : 0.f, e2 = q == 2 ? 1.f : 0.f, e3 = q == 3 ? 1.f : 0.f;
-    const float sa = e0 * s6[0] + e1 * s6[1] + e2 * s6[2] + e3 * s6[3], sb = e0 * s6[4] + e1 * s6[5];
-    const float D = D0 + ctx.quad_sum(sa * Ua + sb * Ub), uu = u0 + ctx.quad_sum(sa * P.ra + sb * P.rb);
-    const float inv = frcp(D);
-    ui = uu * inv;
-    const float Uha = Ua * inv, Uhb = Ub * inv;
-    Uh[0] = ctx.template quad_bcast<0>(Uha); Uh[1] = ctx.template quad_bcast<1>(Uha); Uh[2] = ctx.template quad_bcast<2>(Uha);
-    Uh[3] = ctx.template quad_bcast<3>(Uha); Uh[4] = ctx.template quad_bcast<0>(Uhb); Uh[5] = ctx.template quad_bcast<1>(Uhb);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) { P.a[c] -= Ua * Uh[c]; P.b[c] -= Ub * Uh[c]; }
-    P.ra -= Ua * ui;
-    P.rb -= Ub * ui;
-  }
-  RL_FN void rows_atomic_add(float* w, const Rows& P) const {  // the lane's rows into an accumulator record (every row by exactly one lane)
-    const int q = sub & 3;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) Ctx::limb_atomic_add(w + 8 * q + c, P.a[c]);
-    Ctx::limb_atomic_add(w + 8 * q + 6, P.ra);
-    if (q < 2) {
-#pragma unroll
-      for (int c = 0; c < 6; ++c) Ctx::limb_atomic_add(w + 8 * (q + 4) + c, P.b[c]);
-      Ctx::limb_atomic_add(w + 8 * (q + 4) + 6, P.rb);
-    }
-  }
-  RL_FN void rows_gather(const Rows& P, float (&A)[B6::size], float (&r)[6]) const {  // the whole (symmetric) system into every lane of the quad
-    static_for<0, 6>([&](auto rc) __attribute__((always_inline)) {
-      constexpr int R = decltype(rc)::value, Q = R & 3;
-      static_for<R, 6>([&](auto cc) __attribute__((always_inline)) {
-        constexpr int Cc = decltype(cc)::value;
-        A[B6::at(R, Cc)] = ctx.template quad_bcast<Q>(R < 4 ? P.a[Cc] : P.b[Cc]);
-      });
-      r[R] = ctx.template quad_bcast<Q>(R < 4 ? P.ra : P.rb);
-    });
-  }
   RL_FN static SV ld_sv(const float* w) {  // six words, the first two vectors of a record / per-joint block
     const F4 a = ld4(w), c = ld4(w + 4);
     return SV{{a.x, a.y, a.z}, {a.w, c.x, c.y}};
@@ -1966,33 +1766,6 @@ struct EnvLane {
     return r;
   }
 
-  // P -= (P S)(P S)^T / D etc. for one joint with motion subspace s6 and joint-local terms (D0, u0); returns U / D and u / D
-  RL_FN void eliminate(LinkRec& P, const float (&s6)[6], float D, float uu, float (&Uh)[6], float& ui) const {
-#ifdef RL_PK
-    eliminate_pk(P.A, P.r, s6, D, uu, Uh, ui);
-    return;
-#endif
-    float U6[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      float t = 0.f;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) t += P.A[B6::at(r, c)] * s6[c];
-      U6[r] = t;
-      D += s6[r] * t;
-      uu += s6[r] * P.r[r];
-    }
-    const float inv = frcp(D);
-    ui = uu * inv;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) Uh[r] = U6[r] * inv;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      P.r[r] -= U6[r] * ui;
-#pragma unroll
-      for (int c = r; c < 6; ++c) P.A[B6::at(r, c)] -= U6[r] * Uh[c];
-    }
-  }
   // joint-local terms of joint jx (limb joint j or trunk joint CL + i): armature, implicit PD, limit spring-damper, and the
   // identity row of an inert padding joint
   RL_FN void joint_terms(int jx, bool padding, const float (&tau_e)[JX], const float (&pd_diag)[JX], const float (&pd_rhs)[JX], float& D, float& uu) const {
@@ -2052,10 +1825,9 @@ struct EnvLane {
     ChainTP C = new_chain();
     // Kinematics, and - while a joint's axis and origin are in registers - the motion subspaces, link velocities and bias accelerations
     // along the chain (trunk joints: redundant in all lanes, kept in registers; limb joints: identical in the limb's sub-lanes, parked
-    // in the limb-shared words for the owners of the link groups).  RL_VEL_SEPARATE: the round-3 form, a second pass that reads the
-    // chain words back (A/B).
+    // in the limb-shared words for the owners of the link groups).  (Round 3 did this in a second pass that read the chain words back: two
+    // LDS round trips per joint more.)
     SV Sw[NW], Vw[NW], aw[NW];
-#ifndef RL_VEL_SEPARATE
     if constexpr (KIN_SCAN) {
       kinematics_scan<true>(C, V0, a0, Sw, Vw, aw);
       if (self_on()) ctx.group_sync();  // (self_place reads the limb's chain words: other sub-lanes wrote them)
@@ -2089,48 +1861,6 @@ struct EnvLane {
                  });
     }
     if (self_on()) self_place(C);  // (a lane reads frames of its own limb's words only: written by itself, identically in every sub-lane)
-#else
-    kinematics(C);
-    if (self_on()) self_place(C);  // (a lane reads frames of its own limb's words only: written by itself, identically in every sub-lane)
-    // trunk joints: motion subspaces, link velocities and bias accelerations (redundant in all lanes)
-    {
-      SV Vp = V0, ap = a0;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        V3 axi, pi;
-        C.axp(CL + i, axi, pi);
-        if (i > 0 && ((u.trunk_restart >> i) & 1u)) { Vp = V0; ap = a0; }
-        Sw[i] = SV{axi, cross(pi, axi)};
-        const SV vj = Sw[i] * qd[CL + i];
-        Vw[i] = Vp + vj;
-        aw[i] = ap + crm(Vw[i], vj);
-        Vp = Vw[i];
-        ap = aw[i];
-      }
-    }
-    // limb link velocities / bias accelerations -> limb-shared words (identical in the 4 sub-lanes); env accumulators cleared
-    {
-      SV Vp = V0, ap = a0;
-#pragma unroll
-      for (int i = 0; i < NW; ++i)
-        if (L.attach == i + 1) { Vp = Vw[i]; ap = aw[i]; }
-#pragma unroll
-      for (int j = 0; j < CL; ++j) {
-        V3 ax, pj;
-        C.axp(j, ax, pj);
-        const SV Sj{ax, cross(pj, ax)};
-        const SV vj = Sj * qd[j];
-        const SV Vj = Vp + vj;
-        const SV aj = ap + crm(Vj, vj);
-        float* w = va_words(j);
-        st4(w, F4{Vj.a.x, Vj.a.y, Vj.a.z, Vj.l.x});
-        st4(w + 4, F4{Vj.l.y, Vj.l.z, aj.a.x, aj.a.y});
-        st4(w + 8, F4{aj.a.z, aj.l.x, aj.l.y, aj.l.z});
-        Vp = Vj;
-        ap = aj;
-      }
-    }
-#endif
     // The env's accumulator records (one per trunk link, 0 = the base link) start as the trunk links' own rigid records - plain stores,
     // no clearing pass: the first sub-lane of lane group k owns the trunk links k, k + 4 (a spine of more than three joints has more
     // trunk links than limbs); the persistent external wrench [UPSTREAM B8] rides on its link's record.  Contacts of trunk-link spheres,
@@ -2223,145 +1953,83 @@ struct EnvLane {
     }
     // ---- limb elimination, tip -> attachment (results parked for the outward pass), the limb as seen from its attachment link into the
     // env's accumulator; then the trunk elimination, trunk pieces that hang off the base parked on the way, and the base solve.
-    // ELIM_DIST: the 6 x 6 work of a joint shared by rows among the lanes of a DPP quad (see eliminate_rows); otherwise every sub-lane
-    // eliminates whole records.
+    // Every sub-lane eliminates whole records (REC_STRIDE has what sharing a joint's rows among the lanes of a DPP quad measured).
     RL_PHASE(9, "sub.aba");
     float Uhw[NW][6], uiw[NW];
     float nu0[NB], qdn[JX];
-    if constexpr (ELIM_DIST) {
-      Rows P;
-      rows_zero(P);
-      static_for_down<CL - 1>([&](auto jc) __attribute__((always_inline)) {
-        constexpr int j = decltype(jc)::value;
-        rows_add(this->rec_words(j + 1), P);
-        V3 ax, pj;
-        C.axp(j, ax, pj);
-        const V3 lx = cross(pj, ax);
-        const float s6[6] = {ax.x, ax.y, ax.z, lx.x, lx.y, lx.z};
-        float D, uu, Uh[6], ui;
-        if constexpr (KIN_SCAN) {
-          D = this->ctx.template leg_bcast<j>(D_own);
-          uu = this->ctx.template leg_bcast<j>(uu_own);
-        } else {
-          this->joint_terms(j, j >= this->L.nj, tau_e, pd_diag, pd_rhs, D, uu);
-        }
-        this->eliminate_rows(P, s6, D, uu, Uh, ui);
-        float* o = this->va_words(j);  // (the link velocities parked here are no longer needed)
-        st4(o, F4{Uh[0], Uh[1], Uh[2], Uh[3]});
-        st4(o + 4, F4{Uh[4], Uh[5], ui, 0.f});
-      });
-      if (sub < 4) rows_atomic_add(trunk_words(L.attach), P);  // (eight sub-lanes per limb: its second quad holds a copy)
-      ctx.group_sync();
-      RL_PHASE(10, "sub.cross_leg_sum");
-      rows_zero(P);
-      Rows Pb;  // what the trunk pieces already eliminated hand to the base (a piece ends where its first joint hangs off the base)
-      rows_zero(Pb);
+    LinkRec P;
 #pragma unroll
-      for (int d = NW; d >= 1; --d) {
-        rows_add(trunk_words(d), P);
-        const float s6[6] = {Sw[d - 1].a.x, Sw[d - 1].a.y, Sw[d - 1].a.z, Sw[d - 1].l.x, Sw[d - 1].l.y, Sw[d - 1].l.z};
-        float D, uu;
-        joint_terms(CL + d - 1, d - 1 >= T.nw_used, tau_e, pd_diag, pd_rhs, D, uu);
-        eliminate_rows(P, s6, D, uu, Uhw[d - 1], uiw[d - 1]);
-        if (d > 1 && ((u.trunk_restart >> (d - 1)) & 1u)) {  // (wave-uniform) joint d - 1 hangs off the base: park the piece, the next joint starts another
-          rows_acc(Pb, P);
-          rows_zero(P);
-        }
+    for (int i = 0; i < B6::size; ++i) P.A[i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) P.r[i] = 0.f;
+    // Prefetch: the NEXT joint's link record and axis / origin are in flight while this joint is eliminated (and below: the trunk's
+    // accumulators likewise, the outward pass's U / D, u / D, axes and origins of all limb joints in one batch in front of its chain) -
+    // read where they are consumed, a lone wavefront waits out one LDS round trip per joint, behind stores the compiler cannot move the
+    // reads across: G1 82.05 -> 80.14 us (profiles/r06t_g1_prefetch_ab.txt, r06u_g1_prefetch2_ab.txt).
+    F4 rnext[7];
+    V3 axn{0.f, 0.f, 0.f}, pjn{0.f, 0.f, 0.f};
+    ld_rec(this->rec_words(CL), rnext);
+    C.axp(CL - 1, axn, pjn);
+    static_for_down<CL - 1>([&](auto jc) __attribute__((always_inline)) {
+      constexpr int j = decltype(jc)::value;
+      acc_rec(rnext, P);
+      const V3 ax = axn, pj = pjn;
+      if constexpr (j > 0) {
+        ld_rec(this->rec_words(j), rnext);
+        C.axp(j - 1, axn, pjn);
       }
-      rows_add(trunk_words(0), P);
-      rows_acc(P, Pb);
-      RL_PHASE(11, "sub.trunk_solve");
-      float A6[B6::size], r6[6], n6[6];
-      rows_gather(P, A6, r6);
-      solve6(A6, r6, n6);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) nu0[i] = n6[i];
-    } else {
-      LinkRec P;
-#pragma unroll
-      for (int i = 0; i < B6::size; ++i) P.A[i] = 0.f;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) P.r[i] = 0.f;
-      // REC_PREFETCH: the NEXT joint's link record and axis / origin are in flight while this joint is eliminated (and below: the trunk's
-      // accumulators likewise, the outward pass's U / D, u / D, axes and origins of all limb joints in one batch in front of its chain) -
-      // a lone wavefront otherwise waits out one LDS round trip per joint, behind stores the compiler cannot move the reads across.
-      // G1 82.05 -> 80.14 us (profiles/r06t_g1_prefetch_ab.txt, r06u_g1_prefetch2_ab.txt); -DRL_NO_REC_PREFETCH: read where consumed.
-      F4 rnext[7];
-      V3 axn{0.f, 0.f, 0.f}, pjn{0.f, 0.f, 0.f};
-      if constexpr (REC_PREFETCH) {
-        ld_rec(this->rec_words(CL), rnext);
-        C.axp(CL - 1, axn, pjn);
+      const V3 lx = cross(pj, ax);
+      const float s6[6] = {ax.x, ax.y, ax.z, lx.x, lx.y, lx.z};
+      float D, uu, Uh[6], ui;
+      if constexpr (KIN_SCAN) {
+        D = this->ctx.template leg_bcast<j>(D_own);
+        uu = this->ctx.template leg_bcast<j>(uu_own);
+      } else {
+        this->joint_terms(j, j >= this->L.nj, tau_e, pd_diag, pd_rhs, D, uu);
       }
-      static_for_down<CL - 1>([&](auto jc) __attribute__((always_inline)) {
-        constexpr int j = decltype(jc)::value;
-        V3 ax, pj;
-        if constexpr (REC_PREFETCH) {
-          acc_rec(rnext, P);
-          ax = axn; pj = pjn;
-          if constexpr (j > 0) {
-            ld_rec(this->rec_words(j), rnext);
-            C.axp(j - 1, axn, pjn);
-          }
-        } else {
-          add_rec(this->rec_words(j + 1), P);
-          C.axp(j, ax, pj);
-        }
-        const V3 lx = cross(pj, ax);
-        const float s6[6] = {ax.x, ax.y, ax.z, lx.x, lx.y, lx.z};
-        float D, uu, Uh[6], ui;
-        if constexpr (KIN_SCAN) {
-          D = this->ctx.template leg_bcast<j>(D_own);
-          uu = this->ctx.template leg_bcast<j>(uu_own);
-        } else {
-          this->joint_terms(j, j >= this->L.nj, tau_e, pd_diag, pd_rhs, D, uu);
-        }
-        this->eliminate(P, s6, D, uu, Uh, ui);
-        float* o = this->va_words(j);  // (the link velocities parked here are no longer needed)
-        st4(o, F4{Uh[0], Uh[1], Uh[2], Uh[3]});
-        st4(o + 4, F4{Uh[4], Uh[5], ui, 0.f});
-      });
-      if (sub == 0) atomic_add_rec(trunk_words(L.attach), P);
-      ctx.group_sync();
-      RL_PHASE(10, "sub.cross_leg_sum");
+      eliminate_pk(P.A, P.r, s6, D, uu, Uh, ui);
+      float* o = this->va_words(j);  // (the link velocities parked here are no longer needed)
+      st4(o, F4{Uh[0], Uh[1], Uh[2], Uh[3]});
+      st4(o + 4, F4{Uh[4], Uh[5], ui, 0.f});
+    });
+    if (sub == 0) atomic_add_rec(trunk_words(L.attach), P);
+    ctx.group_sync();
+    RL_PHASE(10, "sub.cross_leg_sum");
 #pragma unroll
-      for (int i = 0; i < B6::size; ++i) P.A[i] = 0.f;
+    for (int i = 0; i < B6::size; ++i) P.A[i] = 0.f;
 #pragma unroll
-      for (int i = 0; i < 6; ++i) P.r[i] = 0.f;
-      LinkRec Pb;  // what the trunk pieces already eliminated hand to the base (a piece ends where its first joint hangs off the base)
+    for (int i = 0; i < 6; ++i) P.r[i] = 0.f;
+    LinkRec Pb;  // what the trunk pieces already eliminated hand to the base (a piece ends where its first joint hangs off the base)
 #pragma unroll
-      for (int i = 0; i < B6::size; ++i) Pb.A[i] = 0.f;
+    for (int i = 0; i < B6::size; ++i) Pb.A[i] = 0.f;
 #pragma unroll
-      for (int i = 0; i < 6; ++i) Pb.r[i] = 0.f;
-      if constexpr (REC_PREFETCH) ld_rec(trunk_words(NW), rnext);
+    for (int i = 0; i < 6; ++i) Pb.r[i] = 0.f;
+    ld_rec(trunk_words(NW), rnext);
 #pragma unroll
-      for (int d = NW; d >= 1; --d) {
-        if constexpr (REC_PREFETCH) {
-          acc_rec(rnext, P);
-          ld_rec(trunk_words(d - 1), rnext);
-        } else add_rec(trunk_words(d), P);
-        const float s6[6] = {Sw[d - 1].a.x, Sw[d - 1].a.y, Sw[d - 1].a.z, Sw[d - 1].l.x, Sw[d - 1].l.y, Sw[d - 1].l.z};
-        float D, uu;
-        joint_terms(CL + d - 1, d - 1 >= T.nw_used, tau_e, pd_diag, pd_rhs, D, uu);
-        eliminate(P, s6, D, uu, Uhw[d - 1], uiw[d - 1]);
-        if (d > 1 && ((u.trunk_restart >> (d - 1)) & 1u)) {  // (wave-uniform) joint d - 1 hangs off the base: park the piece, the next joint starts another
+    for (int d = NW; d >= 1; --d) {
+      acc_rec(rnext, P);
+      ld_rec(trunk_words(d - 1), rnext);
+      const float s6[6] = {Sw[d - 1].a.x, Sw[d - 1].a.y, Sw[d - 1].a.z, Sw[d - 1].l.x, Sw[d - 1].l.y, Sw[d - 1].l.z};
+      float D, uu;
+      joint_terms(CL + d - 1, d - 1 >= T.nw_used, tau_e, pd_diag, pd_rhs, D, uu);
+      eliminate_pk(P.A, P.r, s6, D, uu, Uhw[d - 1], uiw[d - 1]);
+      if (d > 1 && ((u.trunk_restart >> (d - 1)) & 1u)) {  // (wave-uniform) joint d - 1 hangs off the base: park the piece, the next joint starts another
 #pragma unroll
-          for (int i = 0; i < B6::size; ++i) { Pb.A[i] += P.A[i]; P.A[i] = 0.f; }
+        for (int i = 0; i < B6::size; ++i) { Pb.A[i] += P.A[i]; P.A[i] = 0.f; }
 #pragma unroll
-          for (int i = 0; i < 6; ++i) { Pb.r[i] += P.r[i]; P.r[i] = 0.f; }
-        }
+        for (int i = 0; i < 6; ++i) { Pb.r[i] += P.r[i]; P.r[i] = 0.f; }
       }
-      if constexpr (REC_PREFETCH) acc_rec(rnext, P);
-      else add_rec(trunk_words(0), P);
-#pragma unroll
-      for (int i = 0; i < B6::size; ++i) P.A[i] += Pb.A[i];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) P.r[i] += Pb.r[i];
-      RL_PHASE(11, "sub.trunk_solve");
-      float n6[6];
-      solve6(P.A, P.r, n6);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) nu0[i] = n6[i];
     }
+    acc_rec(rnext, P);
+#pragma unroll
+    for (int i = 0; i < B6::size; ++i) P.A[i] += Pb.A[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) P.r[i] += Pb.r[i];
+    RL_PHASE(11, "sub.trunk_solve");
+    float n6[6];
+    solve6(P.A, P.r, n6);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) nu0[i] = n6[i];
     RL_PHASE(12, "sub.back_subst");
     SV Vnew[NIT];
     {
@@ -2395,24 +2063,18 @@ struct EnvLane {
         if (L.grp0_depth == i + 1) vcg = vc;
       }
       vc = vca;
-      F4 po0[CL], po1[CL];
+      F4 po0[CL], po1[CL];  // (the batch of reads in front of the chain: see the prefetch above)
       V3 pax[CL], ppj[CL];
-      if constexpr (REC_PREFETCH) {
 #pragma unroll
-        for (int j = 0; j < CL; ++j) { po0[j] = ld4(va_words(j)); po1[j] = ld4(va_words(j) + 4); }
+      for (int j = 0; j < CL; ++j) { po0[j] = ld4(va_words(j)); po1[j] = ld4(va_words(j) + 4); }
 #pragma unroll
-        for (int j = 0; j < CL; ++j) C.axp(j, pax[j], ppj[j]);
-      }
+      for (int j = 0; j < CL; ++j) C.axp(j, pax[j], ppj[j]);
 #pragma unroll
       for (int j = 0; j < CL; ++j) {
-        F4 o0, o1;
-        if constexpr (REC_PREFETCH) { o0 = po0[j]; o1 = po1[j]; }
-        else { o0 = ld4(va_words(j)); o1 = ld4(va_words(j) + 4); }
+        const F4 o0 = po0[j], o1 = po1[j];
         const float t = o1.z - (o0.x * va[0] + o0.y * va[1] + o0.z * va[2] + o0.w * va[3] + o1.x * va[4] + o1.y * va[5]);
         qdn[j] = t;
-        V3 ax, pj;
-        if constexpr (REC_PREFETCH) { ax = pax[j]; pj = ppj[j]; }
-        else C.axp(j, ax, pj);
+        const V3 ax = pax[j], pj = ppj[j];
         const V3 lx = cross(pj, ax);
         va[0] += ax.x * t; va[1] += ax.y * t; va[2] += ax.z * t;
         va[3] += lx.x * t; va[4] += lx.y * t; va[5] += lx.z * t;

@@ -85,24 +85,14 @@ RL_FN float scalar_term_value(const RewTab& R, const RewEnv& E) {
   return f;
 }
 
-// The term's descriptor.  -DRL_PIN_DESC reads it from the LDS table image into REGISTERS before the evaluation diverges by kind (left
-// to itself the compiler sinks every field's ds_read into the case that uses it: each of the ~16 kinds a wavefront walks through
-// then starts with its own LDS round trip + s_waitcnt).  NOT the default: measured 42.85 vs 42.93 us on A1 Rough 4096 (noise), and
-// the eleven pinned registers at the kernel's pressure peak were enough to bring the reload-under-a-narrowed-EXEC miscompile
-// back on the four-wavefront 3-joint variant (profiles/r03d_pin_desc_miscompile.txt: commands / heading flags of ~1 % of the envs).
-#if defined(__HIP_DEVICE_COMPILE__) && defined(RL_PIN_DESC)
-#define RL_PIN_REG(x) asm volatile("" : "+v"(x))
-#else
-#define RL_PIN_REG(x) ((void)0)
-#endif
-RL_FN RewTab load_rew_desc(const RewTab& src) {
-  RewTab R = src;
-  RL_PIN_REG(R.kind); RL_PIN_REG(R.weight); RL_PIN_REG(R.p[0]); RL_PIN_REG(R.p[1]); RL_PIN_REG(R.p[2]); RL_PIN_REG(R.p[3]);
-  RL_PIN_REG(R.joint_mask); RL_PIN_REG(R.n_idx); RL_PIN_REG(R.body_mask); RL_PIN_REG(R.idx_off); RL_PIN_REG(R.row);
-  return R;
-}
+// The term's descriptor is a plain copy of its table entry: the compiler sinks every field's ds_read into the case that uses it, so each
+// of the ~16 kinds a wavefront walks through starts with its own LDS round trip + s_waitcnt.  (Tried: all eleven fields forced into
+// registers before the evaluation diverges by kind.  42.85 against 42.93 us on A1 Rough 4096 - noise -, and the eleven pinned registers
+// at the kernel's pressure peak brought the reload-under-a-narrowed-EXEC miscompile back on the four-wavefront 3-joint variant: commands /
+// heading flags of ~1 % of the envs, profiles/r03d_pin_desc_miscompile.txt.  Do not pin here.)
+RL_FN RewTab load_rew_desc(const RewTab& src) { return src; }
 
-// unweighted value of one term, evaluated by ONE lane (`R`: a register copy of the descriptor, load_rew_desc)
+// unweighted value of one term, evaluated by ONE lane (`R`: a copy of the descriptor, load_rew_desc)
 template <class TabT>
 RL_FN float term_value(const TabT& T, const Uni& u, const float* __restrict__ terrain, const RewTab& R, const RewEnv& E) {
   const float gate = E.gate, cmd_norm = E.cmd_norm, bv = E.bv, moving = E.moving;
@@ -1174,21 +1164,12 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
   // Which ray does slot s (= lane + LPE * i: what a lane fetches in its i-th load) stand for?  The reference's order - ray s, local x
   // fastest [UPSTREAM B6].  The heightfield is contiguous along WORLD y (hf[ix * ny + iy]), so that order puts the env's consecutive lanes next
   // to each other in memory when the robot looks along world y and a grid ROW apart (16 KB) when it looks along world x, where every lane of a
-  // load touches cache lines of its own.  -DRL_SCAN_YAW_LANES (round 6) makes the slot -> ray map follow the yaw - heading
-  // nearer to world x (|cos| > |sin|): local y fastest - with the set of rays, the value of each ray and its column unchanged.  Measured and
-  // NOT kept: A1 Rough 4096 41.65 -> 43.25 us, Go2 43.87 -> 45.42 us (profiles/r06d_scan_lanes_ab.txt, one call; interpreter kernels of the same sources) - the specialised A1 kernel 35.45 -> 36.97 us with FETCH_SIZE unchanged (9.72 vs 9.74 MiB counted per launch): the lines are L2 hits either way, the two integer
-  // divisions per slot and the scattered LDS row writes cost more than the shared lines save.
-  RL_FN int scan_ray_of_slot(int s, int scan_n, float cy, float sy) const {
-    s = s < scan_n ? s : scan_n - 1;
-#ifndef RL_SCAN_YAW_LANES
-    return s;
-#else
-    const int snx = ctx.uniform_i(T.scan_nx);
-    const float inv_sny = ctx.uniform(1.0f / (float)T.scan_ny);
-    const int ixt = (int)(((float)s + 0.5f) * inv_sny), iyt = s - ixt * ctx.uniform_i(T.scan_ny);  // s = ixt * ny + iyt
-    return fabsf(cy) > fabsf(sy) ? iyt * snx + ixt : s;
-#endif
-  }
+  // load touches cache lines of its own.  (Tried in round 6: a slot -> ray map that follows the yaw - heading nearer to world x (|cos| > |sin|):
+  // local y fastest - with the set of rays, the value of each ray and its column unchanged.  Slower: A1 Rough 4096 41.65 -> 43.25 us, Go2
+  // 43.87 -> 45.42 on the interpreter kernels, the specialised A1 kernel 35.45 -> 36.97 with FETCH_SIZE unchanged (9.72 vs 9.74 MiB counted per
+  // launch), profiles/r06d_scan_lanes_ab.txt: the lines are L2 hits either way, the two integer divisions per slot and the scattered LDS row
+  // writes cost more than the shared lines save.)
+  RL_FN int scan_ray_of_slot(int s, int scan_n) const { return s < scan_n ? s : scan_n - 1; }
   RL_FN void scan_fetch_trip(int r0, int scan_n, float cy, float sy, V3 scan_p, ScanPatches& sp) const {
     const TerrainBase tb = terrain_base(this->u, pos.x, pos.y);  // the root in grid coordinates, once for all the lane's rays
     const int snx = ctx.uniform_i(T.scan_nx);
@@ -1196,7 +1177,7 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
     const float res = T.scan_res, cx0 = 0.5f * (float)(T.scan_nx - 1), cy0 = 0.5f * (float)(T.scan_ny - 1);
 #pragma unroll
     for (int i = 0; i < SCAN_RB; ++i) {
-      const int r = scan_ray_of_slot(r0 + i * LPE, scan_n, cy, sy);
+      const int r = scan_ray_of_slot(r0 + i * LPE, scan_n);
       int iy = (int)(((float)r + 0.5f) * inv_snx), ix = r - iy * snx;  // exact for r < 2^20
       float lx = ((float)ix - cx0) * res, ly = ((float)iy - cy0) * res;
       sp.tp[i] = terrain_fetch(this->u, S.terrain, tb, scan_p.x + cy * lx - sy * ly, scan_p.y + sy * lx + cy * ly);
@@ -1252,7 +1233,7 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
     if (sp.single_trip) {
 #pragma unroll
       for (int i = 0; i < SCAN_RB; ++i) {
-        const int sl = li + i * LPE, r = scan_ray_of_slot(sl, scan_n, cy, sy);
+        const int sl = li + i * LPE, r = scan_ray_of_slot(sl, scan_n);
         const float v = scan_p.z - terrain_height(sp.tp[i]) - soff;
         if (sl < scan_n) stage[scan_off + r] = corrupt ? v : clampf(v, s_lo, s_hi) * s_scale;
       }
@@ -1262,7 +1243,7 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
         scan_fetch_trip(r0, scan_n, cy, sy, scan_p, one);
 #pragma unroll
         for (int i = 0; i < SCAN_RB; ++i) {
-          const int sl = r0 + i * LPE, r = scan_ray_of_slot(sl, scan_n, cy, sy);
+          const int sl = r0 + i * LPE, r = scan_ray_of_slot(sl, scan_n);
           const float v = scan_p.z - terrain_height(one.tp[i]) - soff;
           if (sl < scan_n) stage[scan_off + r] = corrupt ? v : clampf(v, s_lo, s_hi) * s_scale;
         }
@@ -1293,8 +1274,9 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
     }
   }
 
-  // the height-scan loads of the final pose: issued as early as the pose is final (see step_back) and consumed by the group(s) that carry
-  // the scan, after everything else of the observation stage
+  // the height-scan loads of the final pose: issued at the head of the observation stage and consumed by the group(s) that carry the scan,
+  // after everything else of it.  (Tried: issuing them in step_back as soon as the pose is final, ahead of the command update, the push and
+  // the state write-back: A1 38.59 -> 39.20 us, G1 102.90 -> 103.02, profiles/r05b_g1_scan_early_ab.txt.)
   struct ScanAhead {
     ScanPatches sp;
     float cy, sy;
@@ -1371,7 +1353,6 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
     ctx.flush_obs(S.obs_critic, T.critic_dim, 1);
   }
   RL_FN void observations(const ScanAhead& A) {
-#ifndef RL_SPEC_OBS_OFF  // (A/B switch)
     // quadruped instances with several sub-lanes per limb.  (One lane per limb: a group without noise goes straight to HBM - the interpreter's
     // write_group<DIRECT>.  Trunk + limbs instances: the owner-writes are 10 joints x 3 terms x 2 groups by the limb's first sub-lane - more
     // LDS instructions per wavefront than the column tables spread over 32 lanes: G1 102.3 -> 104.3 us, profiles/r05d_spec_obs_ab.txt.)
@@ -1379,7 +1360,6 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
       observations_spec(A);
       return;
     }
-#endif
     derive();
     // the height-scan loads went out first and are consumed by the group(s) that carry the scan, after the feature vector and the
     // non-scan columns.  (Issuing them before the reward stage was tried: the 72 patch registers do not survive it - the compiler
@@ -1632,11 +1612,6 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
       RL_PHASE(19, "resets+commands+push");
     }
     if constexpr (!TAIL) write_dbg_views((terminated || time_out) ? 0.f : 1.f);  // (a split step wrote them in its first launch)
-#ifdef RL_SCAN_EARLY  // (A/B switch) the scan's loads go out HERE: the pose is final (commands and the push below touch velocities only), and the
-    // command update, the push and the write-back of the state then run under their latency
-    ScanAhead scanA;
-    scan_ahead(!TAIL && !ctx.any(terminated || time_out), scanA);
-#endif
     // 7 CommandManager.compute [UPSTREAM B7]
     RL_PHASE(29, "commands");
     {
@@ -1681,11 +1656,7 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
     // 9 observations
     RL_PHASE(20, "observations");
 #ifndef RL_ABL_NO_OBS
-#ifdef RL_SCAN_EARLY
-    observations(scanA);
-#else
     observations(!TAIL && !ctx.any(terminated || time_out));  // (a tail launch starts without the chain words of the trunk + limbs instance)
-#endif
 #endif
     // 10 the episode log of a done env (see DEFER_LOG)
 #ifndef RL_ABL_NO_LOG  // analysis builds: what the log's same-address atomic adds cost a launch in which many envs reset (wrong logs)

@@ -211,16 +211,12 @@ struct WaveCtx {
   // Ordering point for LDS traffic between the lanes of the WAVEFRONT (its LDS region is its own, whatever the workgroup width - only
   // the table image is shared, and that is read-only after the staging barrier).  A wavefront's LDS
   // instructions execute in issue order, so a later ds_read of any lane sees an earlier ds_write of any lane without a hardware
-  // barrier: all that is needed is that the COMPILER keeps the accesses on their side of this point.  __syncthreads() would add
-  // s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier - draining every global load in flight (the terrain and height-scan gathers that
+  // barrier: all that is needed is that the COMPILER keeps the accesses on their side of this point.  __syncthreads(), the old form,
+  // adds s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier - draining every global load in flight (the terrain and height-scan gathers that
   // are deliberately issued early) ~20 times per step.
   __device__ static void wave_sync() {
-#ifdef RL_SYNCTHREADS  // the old form, for A/B runs
-    __syncthreads();
-#else
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#endif
   }
   __device__ void group_sync() const { wave_sync(); }
   __device__ void flush_obs(float* out, int d, int g) const {

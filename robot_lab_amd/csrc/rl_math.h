@@ -61,7 +61,7 @@ RL_FN float opaque(float x) { return x; }
 #endif
 // Two fp32 values in an even-aligned register pair: v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 do both lanes of the pair in the four
 // cycles one v_fma_f32 takes (a scalar operand is broadcast through op_sel, a negation is a source modifier).  Written out by hand where
-// the data IS a stream of pairs (the packed upper triangle of a link record, env_step.h -DRL_PK) - the SLP vectoriser's own pairing
+// the data IS a stream of pairs (the packed upper triangle of a link record, env_step.h eliminate_pk) - the SLP vectoriser's own pairing
 // costs ~90 registers and 14 % of the step (__graft_entry__.py ENV_FLAGS).  Host: two fmaf - the same arithmetic in the same order.
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef float F2p __attribute__((ext_vector_type(2)));

@@ -143,12 +143,8 @@ __device__ inline void layer(const MlpParams& P, int l, const float* __restrict_
 #pragma unroll
       for (int t = 0; t < TPW; ++t)
 #pragma unroll
-        for (int r = 0; r < RT; ++r) {
+        for (int r = 0; r < RT; ++r)  // (hipcc sorts the MFMAs into runs on one accumulator; pinning this issue order with a scheduling barrier per MFMA measured 3 % worse)
           acc[r][t][s & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r][s], b[t][s], acc[r][t][s & 1], 0, 0, 0);
-#ifdef MLP_PIN  // kernel analysis: pin the issue order (hipcc sorts the MFMAs into runs on one accumulator); measured +3 %, i.e. worse
-          __builtin_amdgcn_sched_barrier(0);
-#endif
-        }
   };
   int kb = 0;
   for (; kb + 3 <= KB; kb += 3) {  // rotate the three buffers by unrolling three blocks
