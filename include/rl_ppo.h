@@ -5,7 +5,10 @@
  * RULE is defined by robot_lab_amd/ppo.py (`PPO.update`); this library evaluates the same rule with hand-written gfx950 kernels:
  * gathered-row GEMMs in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) for forward, dX and dW, one loss-head kernel,
  * a fused norm -> clip -> Adam -> floor kernel.  An update only ENQUEUES work on the caller's stream: the KL statistic moves the
- * learning-rate word on the device, Adam reads it there, the statistics accumulate there.  Every reduction has a fixed order
+ * learning-rate word on the device, Adam reads it there, the statistics accumulate there.  The one exception is the FIRST
+ * rl_ppo_minibatch_grad / rl_ppo_update of a handle, with or without a symmetry: it allocates and zeroes the activation, gradient
+ * and partial buffers (hipMalloc + a host-synchronous hipMemset) before it enqueues, so "only enqueues" holds from the second call
+ * on - a caller that captures an update into a graph runs one update outside the capture first.  Every reduction has a fixed order
  * (no floating-point atomics): the same state and permutation give bit-identical parameters.
  *
  * All `*_dev` pointers are DEVICE pointers.  Flat layout (parameters, gradients, Adam moments), the order of
@@ -21,6 +24,7 @@ extern "C" {
 
 #define RL_PPO_MAX_LAYERS 8   /* = RL_MLP_MAX_LAYERS */
 #define RL_PPO_MAX_WIDTH 512  /* = RL_MLP_MAX_WIDTH */
+#define RL_PPO_MAX_SYM 8      /* copies of a symmetry augmentation, the identity included */
 
 enum rl_ppo_activation { RL_PPO_ACT_ELU = 0, RL_PPO_ACT_RELU = 1, RL_PPO_ACT_TANH = 2 }; /* only ELU is implemented; others are refused */
 enum rl_ppo_schedule { RL_PPO_SCHEDULE_FIXED = 0, RL_PPO_SCHEDULE_ADAPTIVE = 1 };
@@ -54,6 +58,20 @@ const char* rl_ppo_last_error(void);
 
 int64_t rl_ppo_num_parameters(const rl_ppo* p);
 
+/* Symmetry data augmentation inside the update (rsl_rl's `use_data_augmentation`; the rule is `PPO(symmetry=...)` of robot_lab_amd/ppo.py).
+ * A mini-batch of n rows is evaluated as n_sym * n rows, copy s in rows s * n .. (s + 1) * n: observations, critic observations and actions
+ * of copy s are S_s(x)[c] = sign[s][c] * x[perm[s][c]], every other stored term is repeated; both losses are means over the n_sym * n rows, the
+ * KL statistic of the adaptive schedule stays the mean over the n stored rows (copy 0).  The mirror is fused into the operand fetch of the
+ * first layer's GEMMs and into the loss head: no mirrored copy of the batch is written to memory.
+ * HOST arrays, perm [n_sym][width] and sign [n_sym][width] (widths: actor input, critic input, actions); a null critic pair = "replicated
+ * unchanged".  Checked before the device is touched, refused with a reason naming the table and the column: n_sym outside 1..RL_PPO_MAX_SYM,
+ * a perm row that is no bijection of the columns, a sign other than +-1, a copy 0 that is not the identity.  Allowed ONCE, before the first
+ * rl_ppo_minibatch_grad / rl_ppo_update (which allocates the activation, gradient and partial buffers, for n_sym * max_rows_per_minibatch rows);
+ * later calls are refused.  `max_rows_per_minibatch` and every n_idx / n_rows keep counting STORED rows.  Never called: the kernels and
+ * the results of a learner without symmetry, bit for bit. */
+int rl_ppo_set_symmetry(rl_ppo* p, int32_t n_sym, const int32_t* obs_perm, const float* obs_sign, const int32_t* critic_perm, const float* critic_sign,
+                        const int32_t* act_perm, const float* act_sign);
+
 /* nn.Linear images ([out][in], [out]) per layer + std[act], device pointers; stream-ordered device-to-device copies.  A null array / pointer
  * skips that part.  set: also what a loaded checkpoint goes through; get: the way back into an `ActorCritic.state_dict()`. */
 int rl_ppo_set_parameters(rl_ppo* p, const float* const* actor_w_dev, const float* const* actor_b_dev, const float* const* critic_w_dev,
@@ -67,7 +85,8 @@ int rl_ppo_parameter_pointers(rl_ppo* p, const float** actor_w_dev, const float*
 int rl_ppo_get_flat(rl_ppo* p, int32_t which, float* dst_dev, void* stream);
 
 /* forward + loss head + backward for the rows idx_dev[0..n_idx) (int64 row numbers into the batch); the gradient of
- * surrogate + value_loss_coef * value_loss - entropy_coef * entropy (means over the n_idx rows) is left in the flat gradient buffer.
+ * surrogate + value_loss_coef * value_loss - entropy_coef * entropy (means over the n_idx rows; with a symmetry set over their n_sym * n_idx
+ * copies) is left in the flat gradient buffer.
  * No optimiser step, no change of the learning rate or the statistics of an update. */
 int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream);
 

@@ -8,6 +8,10 @@
 //   dX        per hidden layer one launch for both networks: dZ_l = (dZ_{l+1} W_l) * elu'(H_l)   (elu' from the stored output: h > 0 ? 1 : h + 1)
 //   dW        ONE launch for every layer of both networks: partial[s] = dZ^T X over the s-th chunk of rows (the deterministic split that
 //             fills the CUs); column sums of dZ (bias gradients, dL/dstd) alike; one reduce launch adds the partials in chunk order
+//   symmetry  (rl_ppo_set_symmetry) a mini-batch of n rows becomes n_sym n VIRTUAL rows, copy s in rows s n .. (s + 1) n: row v reads the
+//             stored row idx[v % n] through the signed column permutation s = v / n.  The mirror lives in the operand fetch of the layer-0
+//             forward and dW problems and in the head's action read (template flag SYM; one table word per column: source column |
+//             sign bit); no mirrored copy of the batch exists in memory, every later stage only sees more rows
 //   step      sum of squares in fixed blocks -> every block of the Adam kernel adds the same partials in the same order: norm, clip
 //             coefficient, Adam, floor of std
 // The three GEMM shapes are one LDS-tiled kernel (128 x 128 output tile, 16-deep slices, four wavefronts of 64 x 64 = 2 x 2
@@ -50,13 +54,23 @@ struct GemmProb {
   int act;        // G_FWD: 1 = ELU follows
   int S, chunk;   // G_DW: number of row chunks, rows per chunk (multiple of TK)
   long cstride;   // G_DW: floats between the partials of consecutive chunks
+  const int* sym; // SYM: [n_sym][columns of X] table words of the gathered operand (SYM_COL | SYM_NEG), or null (G_DW, layers past the first)
+  int n0;         // SYM: stored rows of the mini-batch; virtual row v is copy v / n0 of row gidx[v % n0]
 };
 struct GemmBatch {
   GemmProb p[2 * RL_PPO_MAX_LAYERS];
 };
 
-template <int MODE>
+// a symmetry table word: the source column, and the sign in the float's sign position (the mirror is an exact XOR)
+constexpr int SYM_COL = 0x7fffffff, SYM_NEG = (int)0x80000000u;
+__device__ __forceinline__ float sym_read(const float* row, int word) {
+  return __int_as_float(__float_as_int(row[word & SYM_COL]) ^ (word & SYM_NEG));
+}
+
+// SYM (G_FWD, G_DW of a layer-0 launch): X is read through the symmetry tables, see GemmProb::sym.  SYM = false is the plain gather.
+template <int MODE, bool SYM>
 __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
+  static_assert(!SYM || MODE != G_DX, "only the operands that read X are mirrored");
   const GemmProb& P = batch.p[blockIdx.z];
   if ((int)blockIdx.x >= P.ntiles || (int)blockIdx.y >= (MODE == G_DW ? P.S : 1)) return;  // (uniform for the workgroup)
   __shared__ float As[TK * LD];
@@ -72,12 +86,20 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
   const int b_r = B_RC ? (t & 15) : (t >> 7), b_o = B_RC ? (t >> 4) : (t & 127);
   size_t a_row[8];  // (A_RC) offsets of the eight outer rows
   size_t b_row[8];
+  int a_tab[8];     // (SYM, G_FWD) offset of the row's copy in the table
   if (A_RC) {
     for (int p = 0; p < 8; ++p) {
       const int i = i0 + a_o + 16 * p;
-      a_row[p] = i < P.I ? (size_t)(MODE == G_FWD && P.gidx ? P.gidx[i] : i) * P.lda : 0;
+      if (SYM && MODE == G_FWD) {  // the copy boundary falls anywhere in the tile: copy and row are per element
+        const int s = i < P.I ? i / P.n0 : 0;
+        a_row[p] = i < P.I ? (size_t)P.gidx[i - s * P.n0] * P.lda : 0;
+        a_tab[p] = s * P.R;
+      } else {
+        a_row[p] = i < P.I ? (size_t)(MODE == G_FWD && P.gidx ? P.gidx[i] : i) * P.lda : 0;
+      }
     }
   }
+  const bool b_sym = SYM && MODE == G_DW && P.sym != nullptr;  // (uniform for the workgroup)
   if (B_RC) {
     for (int p = 0; p < 8; ++p) {
       const int j = j0 + b_o + 16 * p;
@@ -86,11 +108,17 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
   }
   float ra[8], rb[8];
   auto fetch = [&](int r0) {
+    int sv = 0, mv = 0;  // (SYM, G_DW) copy and stored-row slot of the virtual row r0 + b_r + 2 p
+    if (b_sym) {
+      sv = (r0 + b_r) / P.n0;
+      mv = (r0 + b_r) - sv * P.n0;
+    }
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
       if (A_RC) {
         const int i = i0 + a_o + 16 * p, r = r0 + a_r;
-        ra[p] = (i < P.I && r < r_end) ? P.A[a_row[p] + r] : 0.f;
+        if (SYM && MODE == G_FWD) ra[p] = (i < P.I && r < r_end) ? sym_read(P.A + a_row[p], P.sym[a_tab[p] + r]) : 0.f;
+        else ra[p] = (i < P.I && r < r_end) ? P.A[a_row[p] + r] : 0.f;
       } else {
         const int i = i0 + a_o, r = r0 + a_r + 2 * p;
         ra[p] = (i < P.I && r < r_end) ? P.A[(size_t)r * P.lda + i] : 0.f;
@@ -101,7 +129,10 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
       } else {
         const int j = j0 + b_o, r = r0 + b_r + 2 * p;
         float v = 0.f;
-        if (j < P.J && r < r_end) {
+        if (b_sym) {
+          if (j < P.J && r < r_end) v = sym_read(P.B + (size_t)P.gidx[mv] * P.ldb, P.sym[sv * P.J + j]);
+          for (mv += 2; mv >= P.n0; mv -= P.n0) ++sv;
+        } else if (j < P.J && r < r_end) {
           const size_t row = MODE == G_DW && P.gidx ? (size_t)P.gidx[r] : (size_t)r;
           v = P.B[row * P.ldb + j];
         }
@@ -231,22 +262,28 @@ struct HeadArgs {
   const float* std;
   float *dmean, *dvalue, *dstd_rows;
   double* partials;  // [blocks][3]: surrogate, value loss, KL sums
-  int n, A;
+  int n, A;          // n: the rows of mean / value (SYM: the n_sym n0 virtual rows)
+  const int* asym;   // SYM: [n_sym][A] table words of the actions
+  int n0;            // SYM: stored rows; virtual row m is copy m / n0 of row idx[m % n0]
   float clip, value_loss_coef, entropy_coef;
   int use_clipped_value_loss;
 };
 
+template <bool SYM>
 __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
   __shared__ double sh[3][256];
   const int m = (int)blockIdx.x * 256 + threadIdx.x;
   double s_sur = 0.0, s_val = 0.0, s_kl = 0.0;
   if (m < a.n) {
-    const size_t g = (size_t)a.idx[m];
     const int A = a.A;
+    const int cp = SYM ? m / a.n0 : 0;  // the copy: every stored term of the row is repeated for it, the action is mirrored
+    const size_t g = (size_t)a.idx[SYM ? m - cp * a.n0 : m];
+    const int* aw = SYM ? a.asym + (size_t)cp * A : nullptr;
+    auto action = [&](int k) { return SYM ? sym_read(a.b.actions + g * A, aw[k]) : a.b.actions[g * A + k]; };
     const float inv_n = 1.0f / (float)a.n;
     float logp = 0.f, kl = 0.f;
     for (int k = 0; k < A; ++k) {
-      const float sd = a.std[k], mu = a.mean[(size_t)m * A + k], d = a.b.actions[g * A + k] - mu;
+      const float sd = a.std[k], mu = a.mean[(size_t)m * A + k], d = action(k) - mu;
       logp += -0.5f * (d * d) / (sd * sd) - logf(sd) - HALF_LOG_2PI;
       const float so = a.b.sigma[g * A + k], dm = a.b.mu[g * A + k] - mu;
       kl += logf(sd / so + 1e-5f) + (so * so + dm * dm) / (2.0f * sd * sd) - 0.5f;
@@ -274,14 +311,14 @@ __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
     }
     a.dvalue[m] = a.value_loss_coef * gv * inv_n;
     for (int k = 0; k < A; ++k) {
-      const float sd = a.std[k], d = a.b.actions[g * A + k] - a.mean[(size_t)m * A + k];
+      const float sd = a.std[k], d = action(k) - a.mean[(size_t)m * A + k];
       a.dmean[(size_t)m * A + k] = c * d / (sd * sd);
       // dlogp / dstd and the entropy bonus (-entropy_coef * mean over rows of sum_k log std_k): the column sum over the rows is dL / dstd_k
       a.dstd_rows[(size_t)m * A + k] = c * (d * d / (sd * sd * sd) - 1.0f / sd) - a.entropy_coef * inv_n / sd;
     }
     s_sur = (double)fmaxf(t1, t2);
     s_val = (double)vloss;
-    s_kl = (double)kl;
+    s_kl = SYM && cp != 0 ? 0.0 : (double)kl;  // the schedule's statistic is that of the stored rows (copy 0)
   }
   sh[0][threadIdx.x] = s_sur; sh[1][threadIdx.x] = s_val; sh[2][threadIdx.x] = s_kl;
   __syncthreads();
@@ -294,7 +331,8 @@ __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
 }
 
 // one workgroup of 64: orders the head's partial sums; with `apply` it books the statistics, moves the learning rate and counts the step
-__global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* partials, int nblocks, int n, const float* std, int A, DevState* st,
+// (n: rows of the loss means; n_kl: rows of the KL mean - the stored rows under symmetry augmentation)
+__global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* partials, int nblocks, int n, int n_kl, const float* std, int A, DevState* st,
                                                             int apply, int adaptive, double desired_kl) {
   __shared__ double sh[3][64];
   for (int q = 0; q < 3; ++q) {
@@ -311,7 +349,7 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* parti
   if (threadIdx.x != 0 || !apply) return;
   float ent = 0.f;
   for (int k = 0; k < A; ++k) ent += 0.5f + HALF_LOG_2PI + logf(std[k]);
-  const float kl = (float)(sh[2][0] / (double)n);
+  const float kl = (float)(sh[2][0] / (double)n_kl);
   st->acc[0] += (double)(float)(sh[1][0] / (double)n);
   st->acc[1] += (double)(float)(sh[0][0] / (double)n);
   st->acc[2] += (double)ent;
@@ -400,19 +438,52 @@ struct rl_ppo {
   int S_std = 1;
   double *head_part = nullptr, *norm_part = nullptr;
   DevState* st = nullptr;
-  std::vector<void*> allocs;
+  std::vector<void*> allocs;      // what lives as long as the handle
+  std::vector<void*> row_allocs;  // what is sized by the rows of a mini-batch (alloc_rows, at the first mini-batch: n_sym is known by then)
+  bool rows_ready = false;
+  int n_sym = 0;                  // 0: rl_ppo_set_symmetry was not called
+  int* sym[3] = {};               // table words [n_sym][width]: observations, critic observations, actions
+  bool started = false;           // a mini-batch was enqueued: the symmetry is fixed from then on
 };
 
 namespace {
 
 template <class T>
-bool dalloc(rl_ppo* p, T** out, size_t count) {
+bool dalloc(std::vector<void*>& owner, T** out, size_t count) {
   void* q = nullptr;
   if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
+  owner.push_back(q);
   if (hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
-  p->allocs.push_back(q);
   *out = (T*)q;
   return true;
+}
+template <class T>
+bool dalloc(rl_ppo* p, T** out, size_t count) {
+  return dalloc(p->allocs, out, count);
+}
+
+// activations, gradients of the activations and the partial buffers for mini-batches of up to `rows` rows (with symmetry: virtual rows)
+bool alloc_rows(rl_ppo* p, size_t rows) {
+  std::vector<void*>& own = p->row_allocs;
+  for (void* q : own) (void)hipFree(q);  // (what a failed earlier attempt left)
+  own.clear();
+  p->rows_ready = false;
+  bool ok = true;
+  const int s_cap = (int)std::max<size_t>(1, (rows + TK - 1) / TK);  // no chunk shorter than a slice
+  for (int k = 0; k < 2 && ok; ++k) {
+    Net& N = p->net[k];
+    for (int l = 0; l < p->L && ok; ++l) {
+      const int Nn = N.dims[l + 1], K = N.dims[l];
+      ok = dalloc(own, &N.h[l + 1], rows * Nn) && dalloc(own, &N.dz[l + 1], rows * Nn);
+      const int tiles = ((Nn + TB - 1) / TB) * ((K + TB - 1) / TB);
+      N.S[l] = std::max(1, std::min(128 / tiles, s_cap));  // ~128 workgroups per layer and network: 1024 in the one dW launch of the A1 networks
+      ok = ok && dalloc(own, &N.part[l], (size_t)N.S[l] * ((size_t)Nn * K + Nn));
+    }
+  }
+  p->S_std = std::max(1, std::min(64, s_cap));
+  p->rows_ready = ok && dalloc(own, &p->dstd_rows, rows * p->A) && dalloc(own, &p->std_part, (size_t)p->S_std * p->A) &&
+                  dalloc(own, &p->head_part, ((rows + 255) / 256) * 3);
+  return p->rows_ready;
 }
 
 int check_launch() {
@@ -426,8 +497,13 @@ int chunk_rows(int n, int S) {  // rows per chunk: a multiple of the GEMM's slic
 }
 
 // the launches of one mini-batch (see the head of this file)
-int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool apply, hipStream_t s) {
+int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool apply, hipStream_t s) {
   const int L = p->L;
+  const bool sym = p->n_sym > 0;
+  const int n = sym ? p->n_sym * n0 : n0;  // the rows every stage past the layer-0 fetch sees
+  if (!p->rows_ready && !alloc_rows(p, (size_t)(sym ? p->n_sym : 1) * (size_t)p->max_rows))
+    return fail("device allocation of the mini-batch buffers failed");  // nothing is launched; a later call tries again
+  p->started = true;
   const float* X[2] = {b->observations, b->privileged_observations};
   for (int l = 0; l < L; ++l) {
     GemmBatch gb{};
@@ -442,9 +518,11 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool 
       g.I = n; g.J = N.dims[l + 1]; g.R = N.dims[l];
       g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
       g.act = l + 1 < L;
+      if (sym && l == 0) { g.sym = p->sym[k]; g.n0 = n0; }
       tiles = std::max(tiles, g.ntiles);
     }
-    hipLaunchKernelGGL(ppo_gemm_kernel<G_FWD>, dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+    if (sym && l == 0) hipLaunchKernelGGL((ppo_gemm_kernel<G_FWD, true>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+    else hipLaunchKernelGGL((ppo_gemm_kernel<G_FWD, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
   }
   {
     HeadArgs a{};
@@ -452,9 +530,11 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool 
     a.dmean = p->net[0].dz[L]; a.dvalue = p->net[1].dz[L]; a.dstd_rows = p->dstd_rows; a.partials = p->head_part;
     a.n = n; a.A = p->A; a.clip = p->hp.clip_param; a.value_loss_coef = p->hp.value_loss_coef; a.entropy_coef = p->hp.entropy_coef;
     a.use_clipped_value_loss = p->hp.use_clipped_value_loss;
+    a.asym = p->sym[2]; a.n0 = n0;
     const int blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(ppo_head_kernel, dim3(blocks), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, s, p->head_part, blocks, n, p->params, p->A, p->st, apply ? 1 : 0,
+    if (sym) hipLaunchKernelGGL(ppo_head_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ppo_head_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, s, p->head_part, blocks, n, n0, p->params, p->A, p->st, apply ? 1 : 0,
                        p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0, p->hp.desired_kl);
   }
   for (int l = L - 1; l >= 1; --l) {
@@ -471,7 +551,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool 
       g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
       tiles = std::max(tiles, g.ntiles);
     }
-    hipLaunchKernelGGL(ppo_gemm_kernel<G_DX>, dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+    hipLaunchKernelGGL((ppo_gemm_kernel<G_DX, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
   }
   {
     GemmBatch gb{};
@@ -490,6 +570,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool 
         g.I = Nn; g.J = K; g.R = n;
         g.tilesJ = (K + TB - 1) / TB; g.ntiles = ((Nn + TB - 1) / TB) * g.tilesJ;
         g.S = N.S[l]; g.chunk = chunk_rows(n, g.S); g.cstride = (long)Nn * K + Nn;
+        if (sym && l == 0) { g.sym = p->sym[k]; g.n0 = n0; }
         ColProb& c = cb.p[np];
         c.Z = N.dz[l + 1]; c.part = N.part[l]; c.N = Nn; c.M = n; c.ld = Nn; c.S = g.S; c.chunk = g.chunk; c.stride = g.cstride; c.off = (long)Nn * K;
         RedProb& r = rb.p[np];
@@ -501,7 +582,8 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n, bool 
     RedProb& r = rb.p[np];
     r.part = p->std_part; r.out = p->grads; r.count = p->A; r.stride = p->A; r.S = p->S_std;
     colx = std::max(colx, (p->A + 63) / 64); Smax = std::max(Smax, p->S_std);
-    hipLaunchKernelGGL(ppo_gemm_kernel<G_DW>, dim3(tiles, Smax, np), dim3(256), 0, s, gb);
+    if (sym) hipLaunchKernelGGL((ppo_gemm_kernel<G_DW, true>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
+    else hipLaunchKernelGGL((ppo_gemm_kernel<G_DW, false>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
     hipLaunchKernelGGL(ppo_colsum_kernel, dim3(colx, Smax, np + 1), dim3(256), 0, s, cb);
     hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)std::min<long>((redmax + 255) / 256, 512), np + 1), dim3(256), 0, s, rb);
   }
@@ -553,6 +635,7 @@ int rl_ppo_destroy(rl_ppo* p) {
   if (!p) return 0;
   (void)hipSetDevice(p->device);
   for (void* q : p->allocs) (void)hipFree(q);
+  for (void* q : p->row_allocs) (void)hipFree(q);
   delete p;
   return 0;
 }
@@ -576,7 +659,6 @@ int rl_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t
   if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed (the HIP learner needs a GPU; there is no CPU path)");
   rl_ppo* p = new rl_ppo();
   p->device = device; p->L = n_layers; p->A = actor_dims[n_layers]; p->max_rows = max_rows_per_minibatch; p->hp = *hyper;
-  const size_t rows = (size_t)max_rows_per_minibatch;
   long off = p->A;  // std first: the order of ActorCritic.parameters()
   for (int k = 0; k < 2; ++k) {
     Net& N = p->net[k];
@@ -589,20 +671,7 @@ int rl_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t
   }
   p->n_params = off;
   bool ok = dalloc(p, &p->params, (size_t)off) && dalloc(p, &p->grads, (size_t)off) && dalloc(p, &p->m1, (size_t)off) && dalloc(p, &p->m2, (size_t)off);
-  const int s_cap = std::max(1, (max_rows_per_minibatch + TK - 1) / TK);  // no chunk shorter than a slice
-  for (int k = 0; k < 2 && ok; ++k) {
-    Net& N = p->net[k];
-    for (int l = 0; l < n_layers && ok; ++l) {
-      const int Nn = N.dims[l + 1], K = N.dims[l];
-      ok = dalloc(p, &N.h[l + 1], rows * Nn) && dalloc(p, &N.dz[l + 1], rows * Nn);
-      const int tiles = ((Nn + TB - 1) / TB) * ((K + TB - 1) / TB);
-      N.S[l] = std::max(1, std::min(128 / tiles, s_cap));  // ~128 workgroups per layer and network: 1024 in the one dW launch of the A1 networks
-      ok = ok && dalloc(p, &N.part[l], (size_t)N.S[l] * ((size_t)Nn * K + Nn));
-    }
-  }
-  p->S_std = std::max(1, std::min(64, s_cap));
-  ok = ok && dalloc(p, &p->dstd_rows, rows * p->A) && dalloc(p, &p->std_part, (size_t)p->S_std * p->A) &&
-       dalloc(p, &p->head_part, (size_t)((max_rows_per_minibatch + 255) / 256) * 3) && dalloc(p, &p->norm_part, (size_t)NORM_BLOCKS) && dalloc(p, &p->st, 1);
+  ok = ok && dalloc(p, &p->norm_part, (size_t)NORM_BLOCKS) && dalloc(p, &p->st, 1);
   if (ok) {
     std::vector<float> ones((size_t)p->A, 1.0f);
     DevState st{};
@@ -619,6 +688,54 @@ int rl_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t
 }
 
 int64_t rl_ppo_num_parameters(const rl_ppo* p) { return p ? p->n_params : 0; }
+
+int rl_ppo_set_symmetry(rl_ppo* p, int32_t n_sym, const int32_t* obs_perm, const float* obs_sign, const int32_t* critic_perm, const float* critic_sign,
+                        const int32_t* act_perm, const float* act_sign) {
+  if (!p) return fail("null argument");
+  if (p->n_sym) return fail("rl_ppo_set_symmetry: the symmetry of this learner is already set (it is set once, before the first mini-batch)");
+  if (p->started)
+    return fail("rl_ppo_set_symmetry: refused after the first rl_ppo_minibatch_grad / rl_ppo_update - the buffers of the handle are sized by the "
+                "number of copies at the first mini-batch; create a new learner");
+  if (n_sym < 1 || n_sym > RL_PPO_MAX_SYM) return fail("rl_ppo_set_symmetry: n_sym " + std::to_string(n_sym) + " outside 1.." + std::to_string(RL_PPO_MAX_SYM));
+  if (!obs_perm || !obs_sign || !act_perm || !act_sign) return fail("rl_ppo_set_symmetry: the observation and action tables are required");
+  if ((critic_perm == nullptr) != (critic_sign == nullptr)) return fail("rl_ppo_set_symmetry: critic_perm and critic_sign are both given or both null");
+  if ((long long)n_sym * p->max_rows > 0x7fffffffLL) return fail("rl_ppo_set_symmetry: n_sym x max_rows_per_minibatch does not fit 32 bits");
+  const char* names[3] = {"obs", "critic", "act"};
+  const int32_t* perm[3] = {obs_perm, critic_perm, act_perm};
+  const float* sign[3] = {obs_sign, critic_sign, act_sign};
+  const int width[3] = {p->net[0].dims[0], p->net[1].dims[0], p->A};
+  std::vector<int> words[3];
+  for (int t = 0; t < 3; ++t) {  // everything is checked before the device is touched: the words index device memory
+    const int W = width[t];
+    words[t].resize((size_t)n_sym * W);
+    std::vector<char> seen((size_t)W);
+    for (int s = 0; s < n_sym; ++s) {
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int c = 0; c < W; ++c) {
+        const std::string at = std::string(names[t]) + " table, copy " + std::to_string(s) + ", column " + std::to_string(c);
+        if (!perm[t]) {  // "replicated": the identity for every copy
+          words[t][(size_t)s * W + c] = c;
+          continue;
+        }
+        const int src = perm[t][(size_t)s * W + c];
+        const float sg = sign[t][(size_t)s * W + c];
+        if (src < 0 || src >= W) return fail("rl_ppo_set_symmetry: " + at + ": source column " + std::to_string(src) + " outside 0.." + std::to_string(W - 1));
+        if (seen[src]) return fail("rl_ppo_set_symmetry: " + at + ": source column " + std::to_string(src) + " is used twice (not a bijection)");
+        seen[src] = 1;
+        if (!(sg == 1.0f || sg == -1.0f)) return fail("rl_ppo_set_symmetry: " + at + ": sign " + std::to_string(sg) + " is not +1 or -1");
+        if (s == 0 && (src != c || sg != 1.0f)) return fail("rl_ppo_set_symmetry: " + at + ": copy 0 must be the identity");
+        words[t][(size_t)s * W + c] = src | (sg < 0.f ? SYM_NEG : 0);
+      }
+    }
+  }
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  bool ok = true;
+  for (int t = 0; t < 3 && ok; ++t)
+    ok = dalloc(p, &p->sym[t], words[t].size()) && hipMemcpy(p->sym[t], words[t].data(), words[t].size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) return fail("rl_ppo_set_symmetry: device allocation of the tables failed (no symmetry is set: the handle is as it was)");
+  p->n_sym = n_sym;  // (the mini-batch buffers are allocated at the first mini-batch, for n_sym x max_rows_per_minibatch rows)
+  return 0;
+}
 
 int rl_ppo_set_parameters(rl_ppo* p, const float* const* actor_w_dev, const float* const* actor_b_dev, const float* const* critic_w_dev,
                           const float* const* critic_b_dev, const float* std_dev, void* stream) {

@@ -64,15 +64,44 @@ class PPO:
 
     def __init__(self, policy: ActorCritic, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01,
                  num_learning_epochs=5, num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0,
-                 group=None):
+                 group=None, symmetry=None):
         self.policy = policy
+        # symmetry data augmentation (rsl_rl `use_data_augmentation=True`): a robot_lab_amd.symmetry.SymmetryTables, or None (the rule below
+        # with one copy - the code path of a learner built without the keyword)
+        if symmetry is not None:
+            from .symmetry import SymmetryTables
+
+            if not isinstance(symmetry, SymmetryTables):
+                raise TypeError(f"PPO: symmetry must be a robot_lab_amd.symmetry.SymmetryTables (or None), not {type(symmetry).__name__}")
+            lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
+            symmetry.check_widths(lin(policy.actor)[0].in_features, lin(policy.critic)[0].in_features, policy.std.numel())
+        self.symmetry = symmetry
+        self._sym_tensors = {}
         self.group = group  # robot_lab_amd.dist.LearnerGroup of a multi-GPU run (rsl_rl's gradient all-reduce); None = single learner
         self.value_loss_coef, self.use_clipped_value_loss, self.clip_param, self.entropy_coef = value_loss_coef, use_clipped_value_loss, clip_param, entropy_coef
         self.num_learning_epochs, self.num_mini_batches = num_learning_epochs, num_mini_batches
         self.learning_rate, self.schedule, self.desired_kl, self.max_grad_norm = learning_rate, schedule, desired_kl, max_grad_norm
         self.optimizer = torch.optim.Adam(policy.parameters(), lr=learning_rate)
 
+    def _mirrored(self, which, x):
+        """THE RULE of the augmentation, for one tensor of a mini-batch: [n, dim] -> [n_sym n, dim], copy s - S_s(x)[c] = sign[s][c] x[perm[s][c]],
+        s = 0 the identity - in rows s n .. (s + 1) n.  A `None` table (the critic's observations) replicates the rows unchanged."""
+        table = getattr(self.symmetry, which)
+        if table is None:
+            return x.repeat(self.symmetry.n_sym, 1)
+        key = (which, x.device, x.dtype)
+        if key not in self._sym_tensors:
+            self._sym_tensors[key] = (torch.as_tensor(table[0].copy(), device=x.device, dtype=torch.long), torch.as_tensor(table[1].copy(), device=x.device, dtype=x.dtype))
+        perm, sign = self._sym_tensors[key]
+        return torch.cat([sign[s] * x[:, perm[s]] for s in range(perm.shape[0])], 0)
+
     def update(self, storage, generator: torch.Generator | None = None) -> dict:
+        """With `symmetry`: every mini-batch of n rows is evaluated on n_sym n rows - observations, critic observations and actions mirrored
+        (`_mirrored`), old log-prob, advantage, return and value of a row repeated for each of its copies; both losses are means over the
+        n_sym n rows (the entropy term does not change: the scalar std is the same for every row); the KL statistic that drives the adaptive
+        learning rate stays the mean over the n stored rows (copy 0) against their stored mu / sigma.  Permutation draw, epochs x
+        mini-batches, gradient clipping, Adam, the floor of std and the `group` all-reduce are those of the plain update.  (`use_mirror_loss`
+        of rsl_rl is not implemented.)"""
         T, N = storage.num_transitions_per_env, storage.num_envs
         flat = lambda t: t.reshape(T * N, *t.shape[2:])  # noqa: E731
         obs, cobs, actions = flat(storage.observations), flat(storage.privileged_observations), flat(storage.actions)
@@ -87,13 +116,19 @@ class PPO:
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
-                mean, std = self.policy.distribution(obs[idx])
-                logp = gaussian_log_prob(actions[idx], mean, std)
-                value = self.policy.critic(cobs[idx]).view(-1)
+                if self.symmetry is None:
+                    mb_obs, mb_cobs, mb_actions, rep = obs[idx], cobs[idx], actions[idx], idx
+                else:
+                    mb_obs, mb_cobs, mb_actions = self._mirrored("obs", obs[idx]), self._mirrored("critic", cobs[idx]), self._mirrored("act", actions[idx])
+                    rep = idx.repeat(self.symmetry.n_sym)  # the stored row of every one of the n_sym n rows
+                n = idx.numel()
+                mean, std = self.policy.distribution(mb_obs)
+                logp = gaussian_log_prob(mb_actions, mean, std)
+                value = self.policy.critic(mb_cobs).view(-1)
                 entropy = gaussian_entropy(std)
                 if self.schedule == "adaptive" and self.desired_kl is not None:
                     with torch.inference_mode():
-                        kl = gaussian_kl(mu_old[idx], sigma_old[idx], mean, std).mean()
+                        kl = gaussian_kl(mu_old[idx], sigma_old[idx], mean[:n], std[:n]).mean()
                         if self.group is not None:
                             kl = self.group.mean(kl)  # the same statistic on every rank -> the same learning rate on every rank
                         if kl > 2.0 * self.desired_kl:
@@ -103,14 +138,14 @@ class PPO:
                         for g in self.optimizer.param_groups:
                             g["lr"] = self.learning_rate
                         stats["kl"] += float(kl)
-                ratio = torch.exp(logp - logp_old[idx])
-                a = adv[idx]
+                ratio = torch.exp(logp - logp_old[rep])
+                a = adv[rep]
                 surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
                 if self.use_clipped_value_loss:
-                    v_clipped = values[idx] + (value - values[idx]).clamp(-self.clip_param, self.clip_param)
-                    value_loss = torch.max((value - returns[idx]) ** 2, (v_clipped - returns[idx]) ** 2).mean()
+                    v_clipped = values[rep] + (value - values[rep]).clamp(-self.clip_param, self.clip_param)
+                    value_loss = torch.max((value - returns[rep]) ** 2, (v_clipped - returns[rep]) ** 2).mean()
                 else:
-                    value_loss = ((returns[idx] - value) ** 2).mean()
+                    value_loss = ((returns[rep] - value) ** 2).mean()
                 loss = surrogate + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
@@ -135,10 +170,12 @@ class PPO:
 class Trainer:
     """collect (HIP, one graph launch) -> update -> push parameters, repeated: `OnPolicyRunner.learn` in miniature.
     `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (single GPU),
-    pushed into the inference kernels device to device; `state_dict()` is rsl_rl's layout with either."""
+    pushed into the inference kernels device to device; `state_dict()` is rsl_rl's layout with either.
+    `symmetry`: symmetry data augmentation inside the update of either learner - a `symmetry.SymmetryTables`, or the mirrors of this
+    env's robot ("lr", "fb", "lr,fb" or a tuple of them), resolved with `symmetry.tables_for_env(env)`."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
-                 critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", **ppo_kw):
+                 critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None, **ppo_kw):
         from .collect import Collector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
@@ -151,6 +188,16 @@ class Trainer:
         if learner not in ("torch", "hip"):
             raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
         self.learner = learner
+        for refused in ("use_mirror_loss", "mirror_loss_coeff"):
+            if refused in ppo_kw:
+                raise NotImplementedError(f"Trainer: {refused} (rsl_rl's mirror loss) is not implemented; symmetry= is the data augmentation only")
+        if symmetry is not None:  # None | SymmetryTables | a mirror spec for this env's robot: "lr", "fb", "lr,fb", ("lr", "fb")
+            from .symmetry import SymmetryTables, tables_for_env
+
+            if not isinstance(symmetry, SymmetryTables):
+                symmetry = tables_for_env(env, symmetry)
+            ppo_kw["symmetry"] = symmetry
+        self.symmetry = symmetry
         if learner == "hip":
             from .ppo_hip import HipPPO
 
@@ -170,7 +217,8 @@ class Trainer:
         self.iteration = 0
 
     def __repr__(self):
-        return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration})"
+        sym = f", symmetry={self.symmetry!r}" if self.symmetry is not None else ""
+        return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration}{sym})"
 
     def state_dict(self):
         """rsl_rl's `ActorCritic.state_dict()` layout; the HIP learner's master parameters are copied back into the module first."""

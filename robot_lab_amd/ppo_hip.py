@@ -11,6 +11,9 @@ inside the update (the learning rate is a device word).  Opt-in: `Trainer(env, l
     alg.push(actor, critic, std)         # new parameters into the inference kernels, device to device (rl_mlp_set_weights_device)
     alg.store_into(policy)               # back into the ActorCritic (checkpoints keep rsl_rl's state_dict layout)
 
+`HipPPO(policy, symmetry=tables)` (a `symmetry.SymmetryTables`, as for `ppo.PPO`): symmetry data augmentation inside the update, the mirror
+fused into the first layer's operand fetch and the loss head (`rl_ppo_set_symmetry`); `max_rows_per_minibatch` keeps counting stored rows.
+
 There is no CPU path and no fall-back to the torch learner: a missing library or an unsupported network raises."""
 from __future__ import annotations
 
@@ -44,7 +47,7 @@ class HipPPO:
 
     def __init__(self, policy, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01, num_learning_epochs=5,
                  num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0, group=None,
-                 max_rows_per_minibatch=None, lib_path: str | None = None):
+                 max_rows_per_minibatch=None, lib_path: str | None = None, symmetry=None):
         import torch
 
         if group is not None:
@@ -72,6 +75,13 @@ class HipPPO:
         if std.device.type != "cuda" or any(p.device != std.device for p in policy.parameters()):
             raise ValueError(f"HipPPO: the policy must live on one CUDA device (std is on {std.device}): the HIP learner has no CPU path - "
                              "move it with policy.to(\"cuda:0\") or use the torch learner, ppo.PPO")
+        if symmetry is not None:
+            from .symmetry import SymmetryTables
+
+            if not isinstance(symmetry, SymmetryTables):
+                raise TypeError(f"HipPPO: symmetry must be a robot_lab_amd.symmetry.SymmetryTables (or None), not {type(symmetry).__name__}")
+            symmetry.check_widths(adims[0], cdims[0], adims[-1])
+        self.symmetry = symmetry
         self.lib = load_ppo_library(lib_path)
         self.actor_dims, self.critic_dims, self.n_layers = adims, cdims, len(adims) - 1
         self.value_loss_coef, self.use_clipped_value_loss, self.clip_param, self.entropy_coef = value_loss_coef, use_clipped_value_loss, clip_param, entropy_coef
@@ -105,10 +115,34 @@ class HipPPO:
                                     int(max_rows), self.device.index or 0, C.byref(handle))
         self._check(rc)
         self.handle, self.max_rows = handle, int(max_rows)
+        if self.symmetry is not None:
+            try:
+                self.set_symmetry(self.symmetry)
+            except Exception:
+                self.close()  # never a learner that quietly runs without the symmetry it was asked for
+                raise
         self.num_parameters = int(self.lib.rl_ppo_num_parameters(self.handle))
         if self._policy is not None:
             self.load_from(self._policy)
             self._policy = None
+
+    def set_symmetry(self, tables):
+        """`rl_ppo_set_symmetry`: once per handle, before its first mini-batch (the constructor's `symmetry=` does it at handle creation)."""
+        import numpy as np
+
+        if self.handle is None:
+            raise RlPpoError("HipPPO.set_symmetry before the handle exists: pass symmetry= to the constructor")
+        ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        keep, args = [], []
+        for t in (tables.obs, tables.critic, tables.act):
+            if t is None:
+                args += [None, None]
+                continue
+            perm, sign = np.ascontiguousarray(t[0], dtype=np.int32), np.ascontiguousarray(t[1], dtype=np.float32)
+            keep += [perm, sign]
+            args += [perm.ctypes.data_as(ip), sign.ctypes.data_as(fp)]
+        self._check(self.lib.rl_ppo_set_symmetry(self.handle, int(tables.n_sym), *args))
+        self.symmetry = tables
 
     def _need(self, rows):
         if self.handle is None:
@@ -244,4 +278,5 @@ class HipPPO:
             pass
 
     def __repr__(self):
-        return f"HipPPO(actor={self.actor_dims}, critic={self.critic_dims}, schedule={self.schedule!r}, lr={self.learning_rate:g}, librl_ppo_hip)"
+        sym = f", symmetry={self.symmetry!r}" if self.symmetry is not None else ""
+        return f"HipPPO(actor={self.actor_dims}, critic={self.critic_dims}, schedule={self.schedule!r}, lr={self.learning_rate:g}{sym}, librl_ppo_hip)"

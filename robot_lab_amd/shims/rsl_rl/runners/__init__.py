@@ -25,8 +25,16 @@ class OnPolicyRunner:
             raise NotImplementedError(f"stand-in runner: ActorCritic + PPO only, got {pol.get('class_name')} / {alg.get('class_name')}")
         if pol.get("activation", "elu") != "elu" or pol.get("actor_obs_normalization") or pol.get("critic_obs_normalization"):
             raise NotImplementedError("stand-in runner: ELU networks without observation normalisation (what every robot_lab agent cfg uses)")
-        if alg.get("symmetry_cfg") or alg.get("rnd_cfg"):
-            raise NotImplementedError("stand-in runner: symmetry augmentation / RND are not wired into the update")
+        sym = alg.get("symmetry_cfg")
+        if sym:
+            get = sym.get if isinstance(sym, dict) else lambda k, d=None: getattr(sym, k, d)  # noqa: E731
+            if get("use_mirror_loss"):
+                raise NotImplementedError("stand-in runner: use_mirror_loss (rsl_rl's mirror loss) is not implemented anywhere in robot_lab_amd")
+            raise NotImplementedError("stand-in runner: a symmetry_cfg carries an arbitrary Python data_augmentation_func, which cannot be turned into the "
+                                      "learners' tables; symmetry data augmentation inside the update is robot_lab_amd.ppo.Trainer(env, symmetry=\"lr\" | "
+                                      "\"lr,fb\" | SymmetryTables) (INTEGRATION.md section 7)")
+        if alg.get("rnd_cfg"):
+            raise NotImplementedError("stand-in runner: RND is not wired into the update")
         # options this stand-in does not implement are refused, never ignored (a silently different learner is worse than none)
         groups = dict(train_cfg.get("obs_groups") or {})
         actor_set = groups.get("policy", groups.get("actor", ["policy"]))

@@ -8,8 +8,14 @@ The batch is collected once by the HIP collector with a freshly initialised poli
 (torch, hip, torch, hip, ...) with device events around each `update()` - which ends in the learner's own read-back of the statistics, so
 the host-side cost of each learner is inside its window - after `--warmup` untimed updates of each.  Reported per learner: median,
 min, max over `--repeat` updates, in ms; and the algorithmic FLOPs of an update (forward + dX + dW of both networks, computed from
-the shapes) over the median.  One JSON line per task.
-    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W]"""
+the shapes) over the median.  One JSON line per task and symmetry setting.
+
+`--symmetry off lr lr,fb`: the same measurement with symmetry data augmentation inside the update (`PPO(symmetry=...)`, `HipPPO(symmetry=...)`),
+both learners with the SAME tables, every setting on the same collected batch in the same process.  The tables are those of
+`symmetry.tables_for_env`; for a robot it has none for (the humanoids) the timing uses random signed permutations with as many copies
+("tables": "random" in the output) - the cost of the gather does not depend on which permutation it is.  Reported beside the times: the HIP
+time over n_sym x the HIP time of the "off" setting of the same run, when "off" is among the settings.
+    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...]"""
 import argparse
 import copy
 import json
@@ -17,12 +23,14 @@ import os
 import statistics
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robot_lab_amd.env import ManagerBasedRLEnv  # noqa: E402
 from robot_lab_amd.ppo import PPO, Trainer  # noqa: E402
 from robot_lab_amd.ppo_hip import HipPPO  # noqa: E402
+from robot_lab_amd.symmetry import SymmetryTables, parse_mirrors, tables_for_env  # noqa: E402
 
 
 def update_flops(alg: HipPPO, rows: int) -> float:
@@ -34,13 +42,47 @@ def update_flops(alg: HipPPO, rows: int) -> float:
     return 2.0 * macs * rows * alg.num_learning_epochs
 
 
-def bench(task, num_envs, repeat, warmup, seed=42):
+def tables(env, spec, dims):
+    """(SymmetryTables | None, "off" | "derived" | "random")"""
+    if spec == "off":
+        return None, "off"
+    try:
+        return tables_for_env(env, spec), "derived"
+    except ValueError as e:
+        if "parse neither" not in str(e):  # only the documented case - a robot whose joint names give no mirror tables - falls back
+            raise
+        print(f"# {spec}: no derived tables for this robot ({str(e)[:60]}...): timing RANDOM signed permutations instead", file=sys.stderr, flush=True)
+        n_sym, rng = 2 ** len(parse_mirrors(spec)), np.random.default_rng(0)
+
+        def rnd(dim):
+            perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
+            return perm, np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
+
+        return SymmetryTables(obs=rnd(dims[0]), critic=rnd(dims[1]), act=rnd(dims[2])), "random"
+
+
+def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42):
     env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
     tr = Trainer(env, seed=seed)
     tr.collector.collect()
     torch.cuda.synchronize()
+    out, hip_off = [], None
+    for spec in symmetry:
+        tab, kind = tables(env, spec, (tr.storage.observations.shape[-1], tr.storage.privileged_observations.shape[-1], env.num_actions))
+        res = bench_one(tr, tab, repeat, warmup, seed)
+        res = dict(task=task, num_envs=num_envs, symmetry=spec, tables=kind, n_sym=tab.n_sym if tab else 1, **res)
+        if spec == "off":
+            hip_off = res["hip"]["median_ms"]
+        elif hip_off:
+            res["hip_over_n_sym_x_off"] = res["hip"]["median_ms"] / (res["n_sym"] * hip_off)
+        out.append(res)
+    env.close()
+    return out
+
+
+def bench_one(tr, tab, repeat, warmup, seed):
     st = tr.storage
-    learners = {"torch": PPO(copy.deepcopy(tr.policy)), "hip": HipPPO(copy.deepcopy(tr.policy))}
+    learners = {"torch": PPO(copy.deepcopy(tr.policy), symmetry=tab), "hip": HipPPO(copy.deepcopy(tr.policy), symmetry=tab)}
     gens = {k: torch.Generator(device="cuda:0").manual_seed(seed) for k in learners}
     times = {k: [] for k in learners}
     for it in range(warmup + repeat):
@@ -55,14 +97,13 @@ def bench(task, num_envs, repeat, warmup, seed=42):
                 times[k].append(t0.elapsed_time(t1))
             assert all(v == v for v in out.values()), (k, out)  # no NaN
     rows = st.num_transitions_per_env * st.num_envs
-    flops = update_flops(learners["hip"], rows)
-    res = dict(task=task, num_envs=num_envs, rows=rows, repeat=repeat, warmup=warmup, update_gflop=flops / 1e9)
+    flops = update_flops(learners["hip"], rows) * (tab.n_sym if tab else 1)
+    res = dict(rows=rows, repeat=repeat, warmup=warmup, update_gflop=flops / 1e9)
     for k, t in times.items():
         med = statistics.median(t)
         res[k] = dict(median_ms=med, min_ms=min(t), max_ms=max(t), tflops_at_median=flops / med / 1e9)
     res["speedup_median"] = res["torch"]["median_ms"] / res["hip"]["median_ms"]
     learners["hip"].close()
-    env.close()
     return res
 
 
@@ -72,11 +113,16 @@ def main():
     ap.add_argument("--num-envs", nargs="+", type=int, default=[4096, 2048])
     ap.add_argument("--repeat", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--symmetry", nargs="+", default=["off"], help="settings to time, each \"off\" or mirrors (lr | fb | lr,fb)")
     a = ap.parse_args()
+    for spec in a.symmetry:
+        if spec != "off":
+            parse_mirrors(spec)
     if len(a.num_envs) != len(a.task):
         ap.error("one --num-envs per --task")
     for task, n in zip(a.task, a.num_envs):
-        print(json.dumps(bench(task, n, a.repeat, a.warmup)), flush=True)
+        for res in bench(task, n, a.repeat, a.warmup, a.symmetry):
+            print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
