@@ -10,6 +10,8 @@
  * and partial buffers (hipMalloc + a host-synchronous hipMemset) before it enqueues, so "only enqueues" holds from the second call
  * on - a caller that captures an update into a graph runs one update outside the capture first.  Every reduction has a fixed order
  * (no floating-point atomics): the same state and permutation give bit-identical parameters.
+ * Symmetry: rl_ppo_set_symmetry (data augmentation) and, on its tables, rl_ppo_set_mirror_loss (rsl_rl's mirror loss, with or without
+ * the augmentation); a handle on which neither was called launches the kernels of a learner without them.
  *
  * All `*_dev` pointers are DEVICE pointers.  Flat layout (parameters, gradients, Adam moments), the order of
  * `ActorCritic.parameters()`: std[act], then per actor layer W[out][in], b[out], then the critic's layers alike. */
@@ -25,6 +27,7 @@ extern "C" {
 #define RL_PPO_MAX_LAYERS 8   /* = RL_MLP_MAX_LAYERS */
 #define RL_PPO_MAX_WIDTH 512  /* = RL_MLP_MAX_WIDTH */
 #define RL_PPO_MAX_SYM 8      /* copies of a symmetry augmentation, the identity included */
+#define RL_PPO_STATS_EX 9     /* entries of rl_ppo_stats_ex */
 
 enum rl_ppo_activation { RL_PPO_ACT_ELU = 0, RL_PPO_ACT_RELU = 1, RL_PPO_ACT_TANH = 2 }; /* only ELU is implemented; others are refused */
 enum rl_ppo_schedule { RL_PPO_SCHEDULE_FIXED = 0, RL_PPO_SCHEDULE_ADAPTIVE = 1 };
@@ -72,6 +75,17 @@ int64_t rl_ppo_num_parameters(const rl_ppo* p);
 int rl_ppo_set_symmetry(rl_ppo* p, int32_t n_sym, const int32_t* obs_perm, const float* obs_sign, const int32_t* critic_perm, const float* critic_sign,
                         const int32_t* act_perm, const float* act_sign);
 
+/* rsl_rl's mirror loss (`use_mirror_loss`, `mirror_loss_coeff`; the rule is `PPO(symmetry=..., mirror_loss=c, data_augmentation=...)` of
+ * robot_lab_amd/ppo.py) on the tables of rl_ppo_set_symmetry: with mu_s the actor's mean on copy s of a row and tau_s = S_s^act(mu_0) held
+ * constant, L_mirror = 1 / ((n_sym - 1) n A) sum over copies s >= 1, rows and action dimensions of (mu_s - tau_s)^2, and the loss gains
+ * coeff * L_mirror.  data_augmentation != 0: on top of the augmented update of rl_ppo_set_symmetry (the mu_s are the means the surrogate
+ * uses).  data_augmentation == 0: surrogate, value loss, entropy and KL are those of a learner WITHOUT symmetry - means over the n stored
+ * rows, the critic is evaluated on n rows - and only the actor is evaluated on the n_sym * n rows, copies >= 1 for L_mirror alone.
+ * Called once, after rl_ppo_set_symmetry and before the first rl_ppo_minibatch_grad / rl_ppo_update; no device work.  Refused with a
+ * reason: no symmetry set, n_sym < 2, a coefficient that is not finite or <= 0, after the first mini-batch, a second call.  Never called:
+ * the kernels and the results of a learner without it, bit for bit. */
+int rl_ppo_set_mirror_loss(rl_ppo* p, float coeff, int32_t data_augmentation);
+
 /* nn.Linear images ([out][in], [out]) per layer + std[act], device pointers; stream-ordered device-to-device copies.  A null array / pointer
  * skips that part.  set: also what a loaded checkpoint goes through; get: the way back into an `ActorCritic.state_dict()`. */
 int rl_ppo_set_parameters(rl_ppo* p, const float* const* actor_w_dev, const float* const* actor_b_dev, const float* const* critic_w_dev,
@@ -86,7 +100,7 @@ int rl_ppo_get_flat(rl_ppo* p, int32_t which, float* dst_dev, void* stream);
 
 /* forward + loss head + backward for the rows idx_dev[0..n_idx) (int64 row numbers into the batch); the gradient of
  * surrogate + value_loss_coef * value_loss - entropy_coef * entropy (means over the n_idx rows; with a symmetry set over their n_sym * n_idx
- * copies) is left in the flat gradient buffer.
+ * copies; + coeff * L_mirror with rl_ppo_set_mirror_loss) is left in the flat gradient buffer.
  * No optimiser step, no change of the learning rate or the statistics of an update. */
 int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream);
 
@@ -97,6 +111,9 @@ int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev,
 /* out[8]: mean value loss, mean surrogate loss, mean entropy, mean KL (0 unless adaptive), learning rate, last pre-clip gradient norm,
  * mini-batches in the last update, Adam step counter.  Waits for `stream`, one small copy. */
 int rl_ppo_stats(rl_ppo* p, double* out, void* stream);
+/* rl_ppo_stats with n_out = RL_PPO_STATS_EX entries: out[0..8) as above, out[8] the mean over the mini-batches of the last update of
+ * L_mirror, before the coefficient (0 without rl_ppo_set_mirror_loss).  The same one wait and one copy. */
+int rl_ppo_stats_ex(rl_ppo* p, double* out, int32_t n_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -212,7 +212,8 @@ class NativeEnv:
 # ---- include/rl_ppo.h: the HIP PPO learner (csrc/rl_ppo.hip -> librl_ppo_hip.so; the host logic is robot_lab_amd/ppo_hip.py) ----------
 PPO_LIB = os.path.join(_HERE, "csrc", "librl_ppo_hip.so")
 PPO_EXPORTS = ["rl_ppo_create", "rl_ppo_destroy", "rl_ppo_last_error", "rl_ppo_num_parameters", "rl_ppo_set_parameters", "rl_ppo_get_parameters",
-               "rl_ppo_parameter_pointers", "rl_ppo_get_flat", "rl_ppo_minibatch_grad", "rl_ppo_update", "rl_ppo_stats", "rl_ppo_set_symmetry"]
+               "rl_ppo_parameter_pointers", "rl_ppo_get_flat", "rl_ppo_minibatch_grad", "rl_ppo_update", "rl_ppo_stats", "rl_ppo_set_symmetry",
+               "rl_ppo_set_mirror_loss", "rl_ppo_stats_ex"]
 _ppo_lib = None
 
 
@@ -255,6 +256,8 @@ def load_ppo_library(path: str | None = None) -> C.CDLL:
     lib.rl_ppo_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
     ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
     lib.rl_ppo_set_symmetry.argtypes = [C.c_void_p, C.c_int32, ip, fp, ip, fp, ip, fp]
+    lib.rl_ppo_set_mirror_loss.argtypes = [C.c_void_p, C.c_float, C.c_int32]
+    lib.rl_ppo_stats_ex.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p]
     if path == PPO_LIB:
         _ppo_lib = lib
     return lib

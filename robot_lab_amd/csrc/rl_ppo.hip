@@ -12,6 +12,11 @@
 //             stored row idx[v % n] through the signed column permutation s = v / n.  The mirror lives in the operand fetch of the layer-0
 //             forward and dW problems and in the head's action read (template flag SYM; one table word per column: source column |
 //             sign bit); no mirrored copy of the batch exists in memory, every later stage only sees more rows
+//   mirror    (rl_ppo_set_mirror_loss) rsl_rl's mirror loss on the same tables: the head's MIRROR instantiation reads, for a row of copy s >= 1,
+//             the target S_s^act(mean of its copy-0 row) from the SAME mean buffer (written by the forward launch before it) and adds
+//             c dL_mirror / dmean to its own row of dmean; a fourth per-block partial carries sum (mu - tau)^2.  Without the augmentation
+//             only the ACTOR's problems keep n_sym n rows: the critic's problems, the std column sum and the loss means are those of the n
+//             stored rows, and a row of a copy >= 1 carries the mirror gradient alone
 //   step      sum of squares in fixed blocks -> every block of the Adam kernel adds the same partials in the same order: norm, clip
 //             coefficient, Adam, floor of std
 // The three GEMM shapes are one LDS-tiled kernel (128 x 128 output tile, 16-deep slices, four wavefronts of 64 x 64 = 2 x 2
@@ -19,6 +24,8 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+
+#include <cmath>
 
 #include <algorithm>
 #include <string>
@@ -254,6 +261,7 @@ struct DevState {
   double grad_norm;    // last pre-clip gradient norm
   long long step;      // Adam step counter
   long long n_minibatches;
+  double mirror_acc;   // sum over the mini-batches of an update of L_mirror (rl_ppo_set_mirror_loss)
 };
 struct HeadArgs {
   const float *mean, *value;  // [n][A], [n]
@@ -267,20 +275,27 @@ struct HeadArgs {
   int n0;            // SYM: stored rows; virtual row m is copy m / n0 of row idx[m % n0]
   float clip, value_loss_coef, entropy_coef;
   int use_clipped_value_loss;
+  // MIRROR: rows below n_terms carry the PPO terms (means over n_terms rows): n with the augmentation, n0 without - then value / dvalue /
+  // dstd_rows hold n0 rows only; rows of copies >= 1 add mirror_coeff dL_mirror / dmean
+  int n_terms;
+  float mirror_coeff;
+  double* mirror_partials;  // [blocks]: sum over the block's rows of copies >= 1 of (mu - tau)^2
 };
 
-template <bool SYM>
+// MIRROR (with SYM): the mirror loss, see HeadArgs::n_terms.  MIRROR = false is the code of a learner without rl_ppo_set_mirror_loss.
+template <bool SYM, bool MIRROR = false>
 __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
+  static_assert(SYM || !MIRROR, "the mirror loss reads the symmetry tables");
   __shared__ double sh[3][256];
   const int m = (int)blockIdx.x * 256 + threadIdx.x;
-  double s_sur = 0.0, s_val = 0.0, s_kl = 0.0;
-  if (m < a.n) {
+  double s_sur = 0.0, s_val = 0.0, s_kl = 0.0, s_mir = 0.0;
+  if (m < a.n && (!MIRROR || m < a.n_terms)) {
     const int A = a.A;
     const int cp = SYM ? m / a.n0 : 0;  // the copy: every stored term of the row is repeated for it, the action is mirrored
     const size_t g = (size_t)a.idx[SYM ? m - cp * a.n0 : m];
     const int* aw = SYM ? a.asym + (size_t)cp * A : nullptr;
     auto action = [&](int k) { return SYM ? sym_read(a.b.actions + g * A, aw[k]) : a.b.actions[g * A + k]; };
-    const float inv_n = 1.0f / (float)a.n;
+    const float inv_n = 1.0f / (float)(MIRROR ? a.n_terms : a.n);
     float logp = 0.f, kl = 0.f;
     for (int k = 0; k < A; ++k) {
       const float sd = a.std[k], mu = a.mean[(size_t)m * A + k], d = action(k) - mu;
@@ -320,6 +335,20 @@ __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
     s_val = (double)vloss;
     s_kl = SYM && cp != 0 ? 0.0 : (double)kl;  // the schedule's statistic is that of the stored rows (copy 0)
   }
+  if (MIRROR && m < a.n && m >= a.n0) {
+    // tau = S_cp^act(mean of the row's copy 0): rows of `mean` that the forward launch wrote and nobody writes here; this thread alone touches
+    // row m of dmean (it wrote the PPO part above, or the row carries no PPO term)
+    const int A = a.A, cp = m / a.n0, n_sym = a.n / a.n0;
+    const float* src = a.mean + (size_t)(m - cp * a.n0) * A;
+    const int* aw = a.asym + (size_t)cp * A;
+    const float scale = a.mirror_coeff * 2.0f / ((float)(n_sym - 1) * (float)a.n0 * (float)A);
+    for (int k = 0; k < A; ++k) {
+      const float diff = a.mean[(size_t)m * A + k] - sym_read(src, aw[k]);
+      const float gm = scale * diff;
+      a.dmean[(size_t)m * A + k] = m < a.n_terms ? a.dmean[(size_t)m * A + k] + gm : gm;
+      s_mir += (double)diff * (double)diff;
+    }
+  }
   sh[0][threadIdx.x] = s_sur; sh[1][threadIdx.x] = s_val; sh[2][threadIdx.x] = s_kl;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -328,6 +357,16 @@ __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
     __syncthreads();
   }
   if (threadIdx.x < 3) a.partials[(size_t)blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
+  if (MIRROR) {  // the fourth partial, through the same tree
+    __syncthreads();
+    sh[0][threadIdx.x] = s_mir;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) sh[0][threadIdx.x] += sh[0][threadIdx.x + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) a.mirror_partials[blockIdx.x] = sh[0][0];
+  }
 }
 
 // one workgroup of 64: orders the head's partial sums; with `apply` it books the statistics, moves the learning rate and counts the step
@@ -361,6 +400,20 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* parti
   }
   st->step += 1;
   st->n_minibatches += 1;
+}
+
+// the mirror loss's statistic: orders the fourth partials and books L_mirror = sum / count (count = (n_sym - 1) n0 A)
+__global__ __launch_bounds__(64) void ppo_mirror_finish_kernel(const double* partials, int nblocks, double count, DevState* st, int apply) {
+  __shared__ double sh[64];
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += 64) s += partials[b];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && apply) st->mirror_acc += (double)(float)(sh[0] / count);
 }
 
 // ---- optimiser step
@@ -444,6 +497,9 @@ struct rl_ppo {
   int n_sym = 0;                  // 0: rl_ppo_set_symmetry was not called
   int* sym[3] = {};               // table words [n_sym][width]: observations, critic observations, actions
   bool started = false;           // a mini-batch was enqueued: the symmetry is fixed from then on
+  float mirror = 0.f;             // coefficient of the mirror loss; 0: rl_ppo_set_mirror_loss was not called
+  bool augment = true;            // (mirror loss) the PPO terms see every copy; false: the stored rows only
+  double* mirror_part = nullptr;  // the head's fourth partials
 };
 
 namespace {
@@ -464,6 +520,7 @@ bool dalloc(rl_ppo* p, T** out, size_t count) {
 
 // activations, gradients of the activations and the partial buffers for mini-batches of up to `rows` rows (with symmetry: virtual rows)
 bool alloc_rows(rl_ppo* p, size_t rows) {
+  const size_t stored = (size_t)p->max_rows;  // what the critic and the std column sum see under a mirror loss without augmentation
   std::vector<void*>& own = p->row_allocs;
   for (void* q : own) (void)hipFree(q);  // (what a failed earlier attempt left)
   own.clear();
@@ -472,9 +529,10 @@ bool alloc_rows(rl_ppo* p, size_t rows) {
   const int s_cap = (int)std::max<size_t>(1, (rows + TK - 1) / TK);  // no chunk shorter than a slice
   for (int k = 0; k < 2 && ok; ++k) {
     Net& N = p->net[k];
+    const size_t rows_k = k == 1 && !p->augment ? stored : rows;
     for (int l = 0; l < p->L && ok; ++l) {
       const int Nn = N.dims[l + 1], K = N.dims[l];
-      ok = dalloc(own, &N.h[l + 1], rows * Nn) && dalloc(own, &N.dz[l + 1], rows * Nn);
+      ok = dalloc(own, &N.h[l + 1], rows_k * Nn) && dalloc(own, &N.dz[l + 1], rows_k * Nn);
       const int tiles = ((Nn + TB - 1) / TB) * ((K + TB - 1) / TB);
       N.S[l] = std::max(1, std::min(128 / tiles, s_cap));  // ~128 workgroups per layer and network: 1024 in the one dW launch of the A1 networks
       ok = ok && dalloc(own, &N.part[l], (size_t)N.S[l] * ((size_t)Nn * K + Nn));
@@ -483,6 +541,7 @@ bool alloc_rows(rl_ppo* p, size_t rows) {
   p->S_std = std::max(1, std::min(64, s_cap));
   p->rows_ready = ok && dalloc(own, &p->dstd_rows, rows * p->A) && dalloc(own, &p->std_part, (size_t)p->S_std * p->A) &&
                   dalloc(own, &p->head_part, ((rows + 255) / 256) * 3);
+  if (p->rows_ready && p->mirror > 0.f) p->rows_ready = dalloc(own, &p->mirror_part, (rows + 255) / 256);
   return p->rows_ready;
 }
 
@@ -501,6 +560,9 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
   const int L = p->L;
   const bool sym = p->n_sym > 0;
   const int n = sym ? p->n_sym * n0 : n0;  // the rows every stage past the layer-0 fetch sees
+  const bool mirror = p->mirror > 0.f;
+  const int n_terms = p->augment ? n : n0;          // rows of the PPO terms, of dstd_rows ...
+  const int rows_of[2] = {n, n_terms};              // ... and of the actor's / the critic's problems
   if (!p->rows_ready && !alloc_rows(p, (size_t)(sym ? p->n_sym : 1) * (size_t)p->max_rows))
     return fail("device allocation of the mini-batch buffers failed");  // nothing is launched; a later call tries again
   p->started = true;
@@ -515,7 +577,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
       g.B = p->params + N.w_off[l]; g.ldb = N.dims[l];
       g.aux = p->params + N.b_off[l];
       g.C = N.h[l + 1]; g.ldc = N.dims[l + 1];
-      g.I = n; g.J = N.dims[l + 1]; g.R = N.dims[l];
+      g.I = rows_of[k]; g.J = N.dims[l + 1]; g.R = N.dims[l];
       g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
       g.act = l + 1 < L;
       if (sym && l == 0) { g.sym = p->sym[k]; g.n0 = n0; }
@@ -531,11 +593,16 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
     a.n = n; a.A = p->A; a.clip = p->hp.clip_param; a.value_loss_coef = p->hp.value_loss_coef; a.entropy_coef = p->hp.entropy_coef;
     a.use_clipped_value_loss = p->hp.use_clipped_value_loss;
     a.asym = p->sym[2]; a.n0 = n0;
+    a.n_terms = n_terms; a.mirror_coeff = p->mirror; a.mirror_partials = p->mirror_part;
     const int blocks = (n + 255) / 256;
-    if (sym) hipLaunchKernelGGL(ppo_head_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+    if (mirror) hipLaunchKernelGGL((ppo_head_kernel<true, true>), dim3(blocks), dim3(256), 0, s, a);
+    else if (sym) hipLaunchKernelGGL(ppo_head_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(ppo_head_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, s, p->head_part, blocks, n, n0, p->params, p->A, p->st, apply ? 1 : 0,
+    hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0, p->params, p->A, p->st, apply ? 1 : 0,
                        p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0, p->hp.desired_kl);
+    if (mirror)
+      hipLaunchKernelGGL(ppo_mirror_finish_kernel, dim3(1), dim3(64), 0, s, p->mirror_part, blocks, (double)(p->n_sym - 1) * (double)n0 * (double)p->A, p->st,
+                         apply ? 1 : 0);
   }
   for (int l = L - 1; l >= 1; --l) {
     GemmBatch gb{};
@@ -547,7 +614,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
       g.B = p->params + N.w_off[l]; g.ldb = N.dims[l];
       g.aux = N.h[l]; g.ldaux = N.dims[l];
       g.C = N.dz[l]; g.ldc = N.dims[l];
-      g.I = n; g.J = N.dims[l]; g.R = N.dims[l + 1];
+      g.I = rows_of[k]; g.J = N.dims[l]; g.R = N.dims[l + 1];
       g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
       tiles = std::max(tiles, g.ntiles);
     }
@@ -567,18 +634,18 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
         g.A = N.dz[l + 1]; g.lda = Nn;
         g.B = l == 0 ? X[k] : N.h[l]; g.gidx = l == 0 ? idx : nullptr; g.ldb = K;
         g.C = N.part[l]; g.ldc = K;
-        g.I = Nn; g.J = K; g.R = n;
+        g.I = Nn; g.J = K; g.R = rows_of[k];
         g.tilesJ = (K + TB - 1) / TB; g.ntiles = ((Nn + TB - 1) / TB) * g.tilesJ;
-        g.S = N.S[l]; g.chunk = chunk_rows(n, g.S); g.cstride = (long)Nn * K + Nn;
+        g.S = N.S[l]; g.chunk = chunk_rows(g.R, g.S); g.cstride = (long)Nn * K + Nn;
         if (sym && l == 0) { g.sym = p->sym[k]; g.n0 = n0; }
         ColProb& c = cb.p[np];
-        c.Z = N.dz[l + 1]; c.part = N.part[l]; c.N = Nn; c.M = n; c.ld = Nn; c.S = g.S; c.chunk = g.chunk; c.stride = g.cstride; c.off = (long)Nn * K;
+        c.Z = N.dz[l + 1]; c.part = N.part[l]; c.N = Nn; c.M = g.R; c.ld = Nn; c.S = g.S; c.chunk = g.chunk; c.stride = g.cstride; c.off = (long)Nn * K;
         RedProb& r = rb.p[np];
         r.part = N.part[l]; r.out = p->grads + N.w_off[l]; r.count = g.cstride; r.stride = g.cstride; r.S = g.S;  // (b follows W in the flat layout)
         tiles = std::max(tiles, g.ntiles); Smax = std::max(Smax, g.S); colx = std::max(colx, (Nn + 63) / 64); redmax = std::max(redmax, r.count);
       }
     ColProb& c = cb.p[np];
-    c.Z = p->dstd_rows; c.part = p->std_part; c.N = p->A; c.M = n; c.ld = p->A; c.S = p->S_std; c.chunk = chunk_rows(n, c.S); c.stride = p->A; c.off = 0;
+    c.Z = p->dstd_rows; c.part = p->std_part; c.N = p->A; c.M = n_terms; c.ld = p->A; c.S = p->S_std; c.chunk = chunk_rows(n_terms, c.S); c.stride = p->A; c.off = 0;
     RedProb& r = rb.p[np];
     r.part = p->std_part; r.out = p->grads; r.count = p->A; r.stride = p->A; r.S = p->S_std;
     colx = std::max(colx, (p->A + 63) / 64); Smax = std::max(Smax, p->S_std);
@@ -737,6 +804,20 @@ int rl_ppo_set_symmetry(rl_ppo* p, int32_t n_sym, const int32_t* obs_perm, const
   return 0;
 }
 
+int rl_ppo_set_mirror_loss(rl_ppo* p, float coeff, int32_t data_augmentation) {
+  if (!p) return fail("null argument");
+  if (p->mirror > 0.f) return fail("rl_ppo_set_mirror_loss: the mirror loss of this learner is already set (it is set once, before the first mini-batch)");
+  if (p->started)
+    return fail("rl_ppo_set_mirror_loss: refused after the first rl_ppo_minibatch_grad / rl_ppo_update - the buffers of the handle are sized at the "
+                "first mini-batch; create a new learner");
+  if (!p->n_sym) return fail("rl_ppo_set_mirror_loss: no symmetry is set (rl_ppo_set_symmetry comes first: its tables say what the mirrored action is)");
+  if (p->n_sym < 2) return fail("rl_ppo_set_mirror_loss: the symmetry of this learner has n_sym = 1 (the identity alone): there is no mirrored copy");
+  if (!std::isfinite(coeff) || !(coeff > 0.f)) return fail("rl_ppo_set_mirror_loss: the coefficient must be finite and > 0, got " + std::to_string(coeff));
+  p->mirror = coeff;  // (no device work: the fourth partials are allocated with the other mini-batch buffers)
+  p->augment = data_augmentation != 0;
+  return 0;
+}
+
 int rl_ppo_set_parameters(rl_ppo* p, const float* const* actor_w_dev, const float* const* actor_b_dev, const float* const* critic_w_dev,
                           const float* const* critic_b_dev, const float* std_dev, void* stream) {
   if (!p) return fail("null argument");
@@ -790,14 +871,15 @@ int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev,
   // the statistics of THIS update start at zero (stream-ordered: the previous update's are read by rl_ppo_stats before)
   if (hipMemsetAsync(p->st->acc, 0, sizeof(double) * 4, s) != hipSuccess || hipMemsetAsync(&p->st->n_minibatches, 0, sizeof(long long), s) != hipSuccess)
     return fail("cannot reset the statistics block");
+  if (p->mirror > 0.f && hipMemsetAsync(&p->st->mirror_acc, 0, sizeof(double), s) != hipSuccess) return fail("cannot reset the statistics block");
   for (int e = 0; e < p->hp.num_learning_epochs; ++e)
     for (int i = 0; i < p->hp.num_mini_batches; ++i)
       if (minibatch(p, batch, perm_dev + (size_t)i * mb, mb, true, s)) return -1;
   return 0;
 }
 
-int rl_ppo_stats(rl_ppo* p, double* out, void* stream) {
-  if (!p || !out) return fail("null argument");
+namespace {
+int read_stats(rl_ppo* p, double* out, int n_out, void* stream) {
   if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("stream synchronisation failed");
   DevState st{};
@@ -805,7 +887,20 @@ int rl_ppo_stats(rl_ppo* p, double* out, void* stream) {
   const double n = st.n_minibatches > 0 ? (double)st.n_minibatches : 1.0;
   out[0] = st.acc[0] / n; out[1] = st.acc[1] / n; out[2] = st.acc[2] / n; out[3] = st.acc[3] / n;
   out[4] = st.lr; out[5] = st.grad_norm; out[6] = (double)st.n_minibatches; out[7] = (double)st.step;
+  if (n_out > 8) out[8] = st.mirror_acc / n;
   return 0;
+}
+}  // namespace
+
+int rl_ppo_stats(rl_ppo* p, double* out, void* stream) {
+  if (!p || !out) return fail("null argument");
+  return read_stats(p, out, 8, stream);
+}
+
+int rl_ppo_stats_ex(rl_ppo* p, double* out, int32_t n_out, void* stream) {
+  if (!p || !out) return fail("null argument");
+  if (n_out != RL_PPO_STATS_EX) return fail("rl_ppo_stats_ex: n_out must be " + std::to_string(RL_PPO_STATS_EX));
+  return read_stats(p, out, n_out, stream);
 }
 
 }  // extern "C"

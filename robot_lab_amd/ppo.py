@@ -13,6 +13,9 @@ library (no copy of it exists here); `tests/test_ppo.py` checks the pieces again
 and it is what makes `tools/train_demo.py` - the end-to-end check that the simulator is a learnable environment - possible."""
 from __future__ import annotations
 
+import math
+import numbers
+
 import torch
 from torch import nn
 
@@ -57,6 +60,23 @@ def gaussian_kl(mu_old, sigma_old, mu, sigma):
     return (torch.log(sigma / sigma_old + 1e-5) + (sigma_old * sigma_old + (mu_old - mu) ** 2) / (2.0 * sigma * sigma) - 0.5).sum(-1)
 
 
+def check_mirror_loss(who, symmetry, mirror_loss, data_augmentation):
+    """(coefficient | None, data_augmentation) of a learner's `mirror_loss=` / `data_augmentation=` keywords, or a ValueError that says why"""
+    data_augmentation = bool(data_augmentation)
+    if mirror_loss is None:
+        if symmetry is not None and not data_augmentation:
+            raise ValueError(f"{who}: data_augmentation=False without mirror_loss leaves the symmetry tables with nothing to do "
+                             "(pass mirror_loss=<coefficient>, or drop symmetry=)")
+        return None, data_augmentation
+    if isinstance(mirror_loss, bool) or not isinstance(mirror_loss, numbers.Real) or not math.isfinite(mirror_loss) or not mirror_loss > 0:
+        raise ValueError(f"{who}: mirror_loss must be None (off) or a finite coefficient > 0, not {mirror_loss!r}")
+    if symmetry is None:
+        raise ValueError(f"{who}: mirror_loss needs symmetry= (the tables that say what the mirrored observation and action are)")
+    if symmetry.n_sym < 2:
+        raise ValueError(f"{who}: mirror_loss needs tables with n_sym >= 2 (the identity alone has no mirrored copy to compare with)")
+    return float(mirror_loss), data_augmentation
+
+
 class PPO:
     """`PPO.update()` of rsl_rl on a `robot_lab_amd.rollout.RolloutStorage` that `Collector.collect()` has filled
     (observations, privileged_observations, actions, values, returns, advantages, actions_log_prob, mu, sigma: [T, N, ...] views of
@@ -64,7 +84,7 @@ class PPO:
 
     def __init__(self, policy: ActorCritic, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01,
                  num_learning_epochs=5, num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0,
-                 group=None, symmetry=None):
+                 group=None, symmetry=None, mirror_loss=None, data_augmentation=True):
         self.policy = policy
         # symmetry data augmentation (rsl_rl `use_data_augmentation=True`): a robot_lab_amd.symmetry.SymmetryTables, or None (the rule below
         # with one copy - the code path of a learner built without the keyword)
@@ -76,6 +96,9 @@ class PPO:
             lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
             symmetry.check_widths(lin(policy.actor)[0].in_features, lin(policy.critic)[0].in_features, policy.std.numel())
         self.symmetry = symmetry
+        # rsl_rl's mirror loss (`use_mirror_loss`, `mirror_loss_coeff`) on the same tables: None (off) or the coefficient; `data_augmentation=False`
+        # keeps the PPO terms on the stored rows (rsl_rl `use_data_augmentation=False`), see `update`
+        self.mirror_loss, self.data_augmentation = check_mirror_loss("PPO", symmetry, mirror_loss, data_augmentation)
         self._sym_tensors = {}
         self.group = group  # robot_lab_amd.dist.LearnerGroup of a multi-GPU run (rsl_rl's gradient all-reduce); None = single learner
         self.value_loss_coef, self.use_clipped_value_loss, self.clip_param, self.entropy_coef = value_loss_coef, use_clipped_value_loss, clip_param, entropy_coef
@@ -100,8 +123,15 @@ class PPO:
         (`_mirrored`), old log-prob, advantage, return and value of a row repeated for each of its copies; both losses are means over the
         n_sym n rows (the entropy term does not change: the scalar std is the same for every row); the KL statistic that drives the adaptive
         learning rate stays the mean over the n stored rows (copy 0) against their stored mu / sigma.  Permutation draw, epochs x
-        mini-batches, gradient clipping, Adam, the floor of std and the `group` all-reduce are those of the plain update.  (`use_mirror_loss`
-        of rsl_rl is not implemented.)"""
+        mini-batches, gradient clipping, Adam, the floor of std and the `group` all-reduce are those of the plain update.
+
+        With `mirror_loss=c` (rsl_rl's `use_mirror_loss`, `mirror_loss_coeff`): mu_s = actor(S_s^obs(o)) for every copy s, the target
+        tau_s = S_s^act(mu_0) DETACHED, L_mirror = mean over copies s >= 1, rows and action dimensions of (mu_s - tau_s)^2 (copy 0 is skipped, as
+        rsl_rl's `mse_loss(mean_actions_batch[n:], actions_mean_symm_batch.detach()[n:])` does), and the loss gains c L_mirror; the result has one
+        more key, `mirror_loss`: the mean over the mini-batches of L_mirror, before the coefficient.  `data_augmentation=True`: the PPO terms are
+        the augmented ones above and the mu_s are the actor outputs the surrogate uses.  `data_augmentation=False`: surrogate, value loss, entropy
+        and KL are those of a learner without symmetry - means over the n stored rows, the critic sees n rows - and the actor is additionally
+        evaluated on copies 1 .. n_sym - 1 for L_mirror alone."""
         T, N = storage.num_transitions_per_env, storage.num_envs
         flat = lambda t: t.reshape(T * N, *t.shape[2:])  # noqa: E731
         obs, cobs, actions = flat(storage.observations), flat(storage.privileged_observations), flat(storage.actions)
@@ -110,6 +140,8 @@ class PPO:
         B = T * N
         mb = B // self.num_mini_batches
         stats = dict(value_loss=0.0, surrogate_loss=0.0, entropy=0.0, kl=0.0)
+        if self.mirror_loss is not None:
+            stats["mirror_loss"] = 0.0
         n_updates = 0
         # rsl_rl's `mini_batch_generator` draws ONE permutation per update and walks it once per epoch
         perm = torch.randperm(B, device=obs.device, generator=generator)
@@ -118,11 +150,17 @@ class PPO:
                 idx = perm[i * mb:(i + 1) * mb]
                 if self.symmetry is None:
                     mb_obs, mb_cobs, mb_actions, rep = obs[idx], cobs[idx], actions[idx], idx
+                elif not self.data_augmentation:  # the actor on every copy (the mirror loss), everything else on the stored rows
+                    mb_obs, mb_cobs, mb_actions, rep = self._mirrored("obs", obs[idx]), cobs[idx], actions[idx], idx
                 else:
                     mb_obs, mb_cobs, mb_actions = self._mirrored("obs", obs[idx]), self._mirrored("critic", cobs[idx]), self._mirrored("act", actions[idx])
                     rep = idx.repeat(self.symmetry.n_sym)  # the stored row of every one of the n_sym n rows
                 n = idx.numel()
                 mean, std = self.policy.distribution(mb_obs)
+                if self.mirror_loss is not None:
+                    mirror = ((mean[n:] - self._mirrored("act", mean[:n].detach())[n:]) ** 2).mean()
+                    if not self.data_augmentation:
+                        mean, std = mean[:n], std[:n]
                 logp = gaussian_log_prob(mb_actions, mean, std)
                 value = self.policy.critic(mb_cobs).view(-1)
                 entropy = gaussian_entropy(std)
@@ -147,6 +185,9 @@ class PPO:
                 else:
                     value_loss = ((returns[rep] - value) ** 2).mean()
                 loss = surrogate + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+                if self.mirror_loss is not None:
+                    loss = loss + self.mirror_loss * mirror
+                    stats["mirror_loss"] += float(mirror.detach())
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 if self.group is not None:
@@ -167,12 +208,21 @@ class PPO:
         return out
 
 
+def mirror_repr(alg):
+    """what a `repr` that prints the symmetry adds for the mirror loss"""
+    if alg.mirror_loss is None:
+        return ""
+    return f", mirror_loss={alg.mirror_loss:g}" + ("" if alg.data_augmentation else ", data_augmentation=False")
+
+
 class Trainer:
     """collect (HIP, one graph launch) -> update -> push parameters, repeated: `OnPolicyRunner.learn` in miniature.
     `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (single GPU),
     pushed into the inference kernels device to device; `state_dict()` is rsl_rl's layout with either.
     `symmetry`: symmetry data augmentation inside the update of either learner - a `symmetry.SymmetryTables`, or the mirrors of this
-    env's robot ("lr", "fb", "lr,fb" or a tuple of them), resolved with `symmetry.tables_for_env(env)`."""
+    env's robot ("lr", "fb", "lr,fb" or a tuple of them), resolved with `symmetry.tables_for_env(env)`.
+    `mirror_loss=c`, `data_augmentation=False` (with `symmetry`; forwarded to the learner): rsl_rl's mirror loss on the same tables, with
+    or without the augmentation - the rule is `PPO.update`'s."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
                  critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None, **ppo_kw):
@@ -190,7 +240,8 @@ class Trainer:
         self.learner = learner
         for refused in ("use_mirror_loss", "mirror_loss_coeff"):
             if refused in ppo_kw:
-                raise NotImplementedError(f"Trainer: {refused} (rsl_rl's mirror loss) is not implemented; symmetry= is the data augmentation only")
+                raise NotImplementedError(f"Trainer: {refused} is rsl_rl's spelling and is not taken here: the mirror loss is "
+                                          "Trainer(..., symmetry=..., mirror_loss=<coefficient>, data_augmentation=True | False)")
         if symmetry is not None:  # None | SymmetryTables | a mirror spec for this env's robot: "lr", "fb", "lr,fb", ("lr", "fb")
             from .symmetry import SymmetryTables, tables_for_env
 
@@ -217,7 +268,7 @@ class Trainer:
         self.iteration = 0
 
     def __repr__(self):
-        sym = f", symmetry={self.symmetry!r}" if self.symmetry is not None else ""
+        sym = f", symmetry={self.symmetry!r}{mirror_repr(self.alg)}" if self.symmetry is not None else ""
         return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration}{sym})"
 
     def state_dict(self):

@@ -13,6 +13,8 @@ inside the update (the learning rate is a device word).  Opt-in: `Trainer(env, l
 
 `HipPPO(policy, symmetry=tables)` (a `symmetry.SymmetryTables`, as for `ppo.PPO`): symmetry data augmentation inside the update, the mirror
 fused into the first layer's operand fetch and the loss head (`rl_ppo_set_symmetry`); `max_rows_per_minibatch` keeps counting stored rows.
+`HipPPO(policy, symmetry=tables, mirror_loss=c, data_augmentation=True | False)`: rsl_rl's mirror loss on the same tables, as `ppo.PPO`
+defines it (`rl_ppo_set_mirror_loss`); `update()` then returns `mirror_loss` too, read in the same one wait (`rl_ppo_stats_ex`).
 
 There is no CPU path and no fall-back to the torch learner: a missing library or an unsupported network raises."""
 from __future__ import annotations
@@ -47,8 +49,10 @@ class HipPPO:
 
     def __init__(self, policy, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01, num_learning_epochs=5,
                  num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0, group=None,
-                 max_rows_per_minibatch=None, lib_path: str | None = None, symmetry=None):
+                 max_rows_per_minibatch=None, lib_path: str | None = None, symmetry=None, mirror_loss=None, data_augmentation=True):
         import torch
+
+        from .ppo import check_mirror_loss
 
         if group is not None:
             raise NotImplementedError("HipPPO is a single-GPU learner: the multi-GPU path (gradient all-reduce over a LearnerGroup) is the torch learner, "
@@ -82,6 +86,8 @@ class HipPPO:
                 raise TypeError(f"HipPPO: symmetry must be a robot_lab_amd.symmetry.SymmetryTables (or None), not {type(symmetry).__name__}")
             symmetry.check_widths(adims[0], cdims[0], adims[-1])
         self.symmetry = symmetry
+        self._mirror = check_mirror_loss("HipPPO", symmetry, mirror_loss, data_augmentation)  # what the handle is given at its creation
+        self.mirror_loss, self.data_augmentation = None, True  # what the handle HAS (set_mirror_loss)
         self.lib = load_ppo_library(lib_path)
         self.actor_dims, self.critic_dims, self.n_layers = adims, cdims, len(adims) - 1
         self.value_loss_coef, self.use_clipped_value_loss, self.clip_param, self.entropy_coef = value_loss_coef, use_clipped_value_loss, clip_param, entropy_coef
@@ -118,6 +124,8 @@ class HipPPO:
         if self.symmetry is not None:
             try:
                 self.set_symmetry(self.symmetry)
+                if self._mirror[0] is not None:
+                    self.set_mirror_loss(*self._mirror)
             except Exception:
                 self.close()  # never a learner that quietly runs without the symmetry it was asked for
                 raise
@@ -143,6 +151,14 @@ class HipPPO:
             args += [perm.ctypes.data_as(ip), sign.ctypes.data_as(fp)]
         self._check(self.lib.rl_ppo_set_symmetry(self.handle, int(tables.n_sym), *args))
         self.symmetry = tables
+
+    def set_mirror_loss(self, coeff, data_augmentation=True):
+        """`rl_ppo_set_mirror_loss`: once per handle, after the symmetry and before the first mini-batch (the constructor's `mirror_loss=`
+        does it at handle creation).  The library checks for itself; a refused call leaves the learner as it was."""
+        if self.handle is None:
+            raise RlPpoError("HipPPO.set_mirror_loss before the handle exists: pass mirror_loss= to the constructor")
+        self._check(self.lib.rl_ppo_set_mirror_loss(self.handle, float(coeff), int(bool(data_augmentation))))
+        self.mirror_loss, self.data_augmentation = float(coeff), bool(data_augmentation)
 
     def _need(self, rows):
         if self.handle is None:
@@ -261,10 +277,19 @@ class HipPPO:
         rows = perm.numel()
         self._need(rows // self.num_mini_batches)
         self._check(self.lib.rl_ppo_update(self.handle, C.byref(b), C.c_void_p(perm.data_ptr()), rows, self._stream()))
-        out = (C.c_double * 8)()
-        self._check(self.lib.rl_ppo_stats(self.handle, out, self._stream()))  # the one wait of the update (keeps `keep` / `perm` alive until then)
+        # the one wait of the update (keeps `keep` / `perm` alive until then)
+        if self.mirror_loss is None:
+            out = (C.c_double * 8)()
+            self._check(self.lib.rl_ppo_stats(self.handle, out, self._stream()))
+        else:
+            out = (C.c_double * 9)()
+            self._check(self.lib.rl_ppo_stats_ex(self.handle, out, 9, self._stream()))
         self.learning_rate, self.last_grad_norm = float(out[4]), float(out[5])
-        return dict(value_loss=float(out[0]), surrogate_loss=float(out[1]), entropy=float(out[2]), kl=float(out[3]), learning_rate=self.learning_rate)
+        res = dict(value_loss=float(out[0]), surrogate_loss=float(out[1]), entropy=float(out[2]), kl=float(out[3]))
+        if self.mirror_loss is not None:
+            res["mirror_loss"] = float(out[8])
+        res["learning_rate"] = self.learning_rate
+        return res
 
     def close(self):
         if getattr(self, "handle", None):
@@ -278,5 +303,7 @@ class HipPPO:
             pass
 
     def __repr__(self):
-        sym = f", symmetry={self.symmetry!r}" if self.symmetry is not None else ""
+        from .ppo import mirror_repr
+
+        sym = f", symmetry={self.symmetry!r}{mirror_repr(self)}" if self.symmetry is not None else ""
         return f"HipPPO(actor={self.actor_dims}, critic={self.critic_dims}, schedule={self.schedule!r}, lr={self.learning_rate:g}{sym}, librl_ppo_hip)"

@@ -28,11 +28,10 @@ class OnPolicyRunner:
         sym = alg.get("symmetry_cfg")
         if sym:
             get = sym.get if isinstance(sym, dict) else lambda k, d=None: getattr(sym, k, d)  # noqa: E731
-            if get("use_mirror_loss"):
-                raise NotImplementedError("stand-in runner: use_mirror_loss (rsl_rl's mirror loss) is not implemented anywhere in robot_lab_amd")
+            mirror = ", mirror_loss=<mirror_loss_coeff>, data_augmentation=<use_data_augmentation>" if get("use_mirror_loss") else ""
             raise NotImplementedError("stand-in runner: a symmetry_cfg carries an arbitrary Python data_augmentation_func, which cannot be turned into the "
-                                      "learners' tables; symmetry data augmentation inside the update is robot_lab_amd.ppo.Trainer(env, symmetry=\"lr\" | "
-                                      "\"lr,fb\" | SymmetryTables) (INTEGRATION.md section 7)")
+                                      "learners' tables; symmetry data augmentation and the mirror loss inside the update are "
+                                      f"robot_lab_amd.ppo.Trainer(env, symmetry=\"lr\" | \"lr,fb\" | SymmetryTables{mirror}) (INTEGRATION.md section 7)")
         if alg.get("rnd_cfg"):
             raise NotImplementedError("stand-in runner: RND is not wired into the update")
         # options this stand-in does not implement are refused, never ignored (a silently different learner is worse than none)

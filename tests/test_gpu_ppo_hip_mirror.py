@@ -1,0 +1,371 @@
+"""`-m gpu`: rsl_rl's mirror loss inside the HIP PPO learner (`rl_ppo_set_mirror_loss`, the MIRROR instantiation of the loss head in
+csrc/rl_ppo.hip, `ppo_hip.HipPPO(symmetry=..., mirror_loss=..., data_augmentation=...)`) against the torch learner of robot_lab_amd/ppo.py.
+
+Setup and bounds are those of tests/test_gpu_ppo_hip_symmetry.py (its helpers are restated here): ActorCritic(45, 235, 12), a `_fake_storage`
+with T = 24, N = 256, parameters perturbed, random signed-permutation tables from `default_rng(11)`, coefficient 0.5.  The comparator is
+`ppo.PPO(symmetry=..., mirror_loss=..., data_augmentation=...)` in fp64 - its rule is pinned to the formula by tests/test_ppo_mirror_loss.py -
+and the same in fp32 measures what fp32 round-off alone does (d); never the HIP learner itself.
+Bounds: per gradient tensor e <= max(8 d, one fp32 spacing of max|g64| relative to it); after an update q999 <= max(8 q999_32, ulp),
+max <= sum of the learning rates; statistics within 8 x the fp32 learner's own error + 1e-6 relative.
+Two modes: (a) with the data augmentation (every stage sees the n_sym n rows), (b) without (the critic, the std column sum and the loss means see the
+n stored rows, the actor n_sym n)."""
+import copy
+import types
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+T, N, OD, CD, A = 24, 256, 45, 235, 12
+B, MB = T * N, T * N // 4
+DEV = "cuda:0"
+PERTURB_SEED = 1  # with it the fp64 and the fp32 torch learner walk the same 20-step learning-rate path in both modes (asserted below)
+COEFF = 0.5
+
+
+def _fake_storage(policy, T, N, od, cd, A, seed=0):
+    """`_fake_storage` of tests/test_ppo.py (action dimension 0 being positive is "good")"""
+    import torch
+
+    from robot_lab_amd.ppo import gaussian_log_prob
+
+    g = torch.Generator().manual_seed(seed)
+    obs, cobs = torch.randn(T, N, od, generator=g), torch.randn(T, N, cd, generator=g)
+    with torch.no_grad():
+        mu, sd = policy.distribution(obs)
+        act = mu + sd * torch.randn(mu.shape, generator=g)
+        logp = gaussian_log_prob(act, mu, sd)
+        val = policy.critic(cobs).squeeze(-1)
+    adv = act[..., 0].clone()
+    adv = (adv - adv.mean()) / adv.std()
+    ret = val + adv
+    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
+                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
+
+
+def _cast(st, dtype):
+    import torch
+
+    out = types.SimpleNamespace(num_transitions_per_env=st.num_transitions_per_env, num_envs=st.num_envs)
+    for k, v in vars(st).items():
+        if torch.is_tensor(v):
+            setattr(out, k, v.to(device=DEV, dtype=dtype))
+    return out
+
+
+def _random_table(rng, n_sym, dim):
+    perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
+    sign = np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
+    return perm, sign
+
+
+def _tables(n_sym, critic=True, seed=11):
+    from robot_lab_amd.symmetry import SymmetryTables
+
+    rng = np.random.default_rng(seed)
+    obs, cri, act = _random_table(rng, n_sym, OD), _random_table(rng, n_sym, CD), _random_table(rng, n_sym, A)
+    return SymmetryTables(obs=obs, critic=cri if critic else None, act=act)
+
+
+def _rows(st, idx):
+    """the rows `idx` of a `_cast` storage as a 1 x len(idx) storage: one epoch of one mini-batch of the torch learner is then the gradient on them"""
+    import torch
+
+    out = types.SimpleNamespace(num_transitions_per_env=1, num_envs=len(idx))
+    for k, v in vars(st).items():
+        if torch.is_tensor(v):
+            setattr(out, k, v.reshape(B, -1)[idx].unsqueeze(0).contiguous())
+    return out
+
+
+@pytest.fixture(scope="module")
+def case():
+    import torch
+
+    from robot_lab_amd.ppo import ActorCritic
+
+    torch.manual_seed(0)
+    pol = ActorCritic(OD, CD, A)
+    st = _fake_storage(pol, T, N, OD, CD, A)
+    g = torch.Generator().manual_seed(PERTURB_SEED)
+    with torch.no_grad():
+        for p in pol.parameters():
+            p.add_(0.01 * torch.randn(p.shape, generator=g) * p.abs().mean())
+    zero_adv = copy.copy(st)  # the same batch with every advantage zero: with both coefficients zero too, only the mirror term is left
+    zero_adv.advantages = torch.zeros_like(st.advantages)
+    return pol, st, zero_adv
+
+
+def _gen(seed=1):
+    import torch
+
+    return torch.Generator(device=DEV).manual_seed(seed)
+
+
+def _perm(seed=1):
+    import torch
+
+    return torch.randperm(B, device=DEV, generator=_gen(seed))
+
+
+def _torch_learner(pol, dtype, **kw):
+    """the torch learner on a copy of `pol`; records the learning rate in force at every optimiser step"""
+    from robot_lab_amd.ppo import PPO
+
+    p = copy.deepcopy(pol).to(device=DEV, dtype=dtype)
+    alg = PPO(p, **kw)
+    alg.lr_path = []
+    step = alg.optimizer.step
+
+    def recording_step(*a, **k):
+        alg.lr_path.append(alg.optimizer.param_groups[0]["lr"])
+        return step(*a, **k)
+
+    alg.optimizer.step = recording_step
+    return alg
+
+
+def _split(flat, pol):
+    out, o = {}, 0
+    for name, p in pol.named_parameters():
+        out[name] = flat[o:o + p.numel()].double().cpu()
+        o += p.numel()
+    assert o == flat.numel()
+    return out
+
+
+_REFERENCES = {}
+
+
+def _reference(pol, st, rows, n_sym, critic, augment, **kw):
+    """{dtype: {tensor: gradient}} of the torch learner with the mirror loss on the first `rows` rows of the test's permutation, computed once per
+    setting and shared (never modified) by the tests that need it"""
+    import torch
+
+    key = (id(st), rows, n_sym, critic, augment, tuple(sorted(kw.items())))
+    if key not in _REFERENCES:
+        tab, idx, ref = _tables(n_sym, critic), _perm()[:rows], {}
+        for dtype in (torch.float64, torch.float32):
+            alg = _torch_learner(pol, dtype, num_learning_epochs=1, num_mini_batches=1, max_grad_norm=1e30, symmetry=tab, mirror_loss=COEFF,
+                                 data_augmentation=augment, **kw)
+            alg.update(_rows(_cast(st, dtype), idx), _gen(5))
+            ref[dtype] = {n: p.grad.detach().double().cpu() for n, p in alg.policy.named_parameters()}
+        _REFERENCES[key] = ref
+    return _REFERENCES[key]
+
+
+def _compare(title, g_hip, ref, only=None):
+    """prints the table, returns the tensors above e <= max(8 d, one fp32 spacing of max|g64| relative to it)"""
+    import torch
+
+    print(f"\n{title}\n{'tensor':<18}{'max|g64|':>12}{'e (hip)':>12}{'d (torch32)':>13}{'e/d':>8}{'floor':>12}")
+    bad = []
+    for n, g64 in ref[torch.float64].items():
+        if only is not None and not n.startswith(only):
+            continue
+        scale = g64.abs().max().item()
+        assert scale > 0, n
+        e = (g_hip[n].reshape(g64.shape) - g64).abs().max().item() / scale
+        d = (ref[torch.float32][n] - g64).abs().max().item() / scale
+        floor = float(np.spacing(np.float32(scale))) / scale
+        print(f"{n:<18}{scale:12.4e}{e:12.3e}{d:13.3e}{e / d if d else float('inf'):8.2f}{floor:12.3e}")
+        if not e <= max(8 * d, floor):
+            bad.append((n, e, d, floor))
+    return bad
+
+
+MODES = {"a": True, "b": False}  # data_augmentation
+
+
+@pytest.mark.parametrize("mode,rows,n_sym,critic", [("a", 1000, 4, True), ("a", 37, 2, True), ("b", 1000, 3, True), ("b", 37, 2, True), ("b", MB, 2, False)],
+                         ids=["a-1000x4", "a-37x2", "b-1000x3", "b-37x2", "b-1536x2-critic-replicated"])
+def test_gradient_parity_with_mirror_loss(case, mode, rows, n_sym, critic):
+    """(the table is profiles/ppo_hip_mirror_grad_parity.txt).  Mode (a), 1000 rows x 4 copies: the copy boundaries fall inside a 128-row tile, a
+    16-row slice, a 256-row head block (1000 = 3 * 256 + 232: a block holds rows of two copies) and the dW chunks; 37 x 2: one partial tile, copy 1
+    reads copy 0's rows of `mean` inside the same head block.  Mode (b), 1000 x 3 and 37 x 2: the critic's problems have n0 rows where the actor's
+    have n_sym n0; 1536 x 2 with `critic=None`: the whole first mini-batch."""
+    import torch
+
+    from robot_lab_amd.ppo_hip import HipPPO
+
+    pol, st, _ = case
+    augment = MODES[mode]
+    ref = _reference(pol, st, rows, n_sym, critic, augment)
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=MB, symmetry=_tables(n_sym, critic), mirror_loss=COEFF, data_augmentation=augment)
+    assert ("mirror_loss=0.5" + ("" if augment else ", data_augmentation=False")) in repr(hip) and ("data_augmentation" in repr(hip)) == (not augment)
+    g_hip = _split(hip.minibatch_grad(_cast(st, torch.float32), _perm()[:rows]), pol)
+    torch.cuda.synchronize()
+    bad = _compare(f"mode ({mode}), {rows} rows x {n_sym} copies{'' if critic else ', critic replicated'}", g_hip, ref)
+    assert not bad, f"gradient error above 8 x the fp32 torch learner's: {bad}"
+    hip.close()
+
+
+@pytest.mark.parametrize("rows,n_sym", [(37, 2), (1000, 3)], ids=["37x2", "1000x3"])
+def test_the_mirror_term_alone(case, rows, n_sym):
+    """every advantage zero, value_loss_coef = entropy_coef = 0, mode (b): the loss is c L_mirror.  The actor's gradients are held to the bound;
+    every critic tensor and std must be EXACTLY zero - a mirrored row leaking into the value or the std path would show here."""
+    import torch
+
+    from robot_lab_amd.ppo_hip import HipPPO
+
+    pol, _, zero_adv = case
+    off = dict(value_loss_coef=0.0, entropy_coef=0.0)
+    ref = _reference(pol, zero_adv, rows, n_sym, True, False, **off)
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=MB, symmetry=_tables(n_sym), mirror_loss=COEFF, data_augmentation=False, **off)
+    g_hip = _split(hip.minibatch_grad(_cast(zero_adv, torch.float32), _perm()[:rows]), pol)
+    torch.cuda.synchronize()
+    bad = _compare(f"the mirror term alone, {rows} rows x {n_sym} copies", g_hip, ref, only="actor")
+    assert not bad, bad
+    for n, g in g_hip.items():
+        if not n.startswith("actor"):
+            assert bool((g == 0).all()), (n, g.abs().max().item())
+            assert bool((ref[torch.float64][n] == 0).all()), n  # (so says the rule)
+    hip.close()
+
+
+def test_no_stale_rows(case):
+    """one handle, mode (b): a mini-batch of 1000 rows, then one of 37 - nothing may depend on what the larger one left in the buffers"""
+    import torch
+
+    from robot_lab_amd.ppo_hip import HipPPO
+
+    pol, st, _ = case
+    ref = _reference(pol, st, 37, 2, True, False)
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=MB, symmetry=_tables(2), mirror_loss=COEFF, data_augmentation=False)
+    st32 = _cast(st, torch.float32)
+    hip.minibatch_grad(st32, _perm()[:1000])
+    g_hip = _split(hip.minibatch_grad(st32, _perm()[:37]), pol)
+    torch.cuda.synchronize()
+    bad = _compare("mode (b), 37 rows x 2 copies after 1000 rows on the same handle", g_hip, ref)
+    assert not bad, bad
+    hip.close()
+
+
+@pytest.mark.parametrize("mode", ["a", "b"])
+def test_one_update_with_mirror_loss_matches_the_torch_learner(case, mode):
+    """(the table is profiles/ppo_hip_mirror_update_parity.txt)"""
+    import torch
+
+    from robot_lab_amd.ppo_hip import HipPPO
+
+    pol, st, _ = case
+    kw = dict(symmetry=_tables(2), mirror_loss=COEFF, data_augmentation=MODES[mode])
+    a64, a32 = _torch_learner(pol, torch.float64, **kw), _torch_learner(pol, torch.float32, **kw)
+    s64, s32 = a64.update(_cast(st, torch.float64), _gen()), a32.update(_cast(st, torch.float32), _gen())
+    assert len(a64.lr_path) == 20 and a64.lr_path == a32.lr_path, "the two torch references took different learning-rate paths: the inputs are mis-chosen"
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), **kw)
+    s_hip = hip.update(_cast(st, torch.float32), _gen())
+    out = hip.store_into(copy.deepcopy(pol).to(DEV))
+    torch.cuda.synchronize()
+    p64 = {n: p.detach().double().cpu() for n, p in a64.policy.named_parameters()}
+    p32 = {n: p.detach().double().cpu() for n, p in a32.policy.named_parameters()}
+    ph = {n: p.detach().double().cpu() for n, p in out.named_parameters()}
+    displacement = float(sum(a64.lr_path))  # Adam moves an entry by at most lr per step
+    print(f"\nmode ({mode}), one update of 5 x 4 mini-batches, n_sym = 2\n{'tensor':<18}{'q999 hip':>12}{'q999 torch32':>14}{'max hip':>12}{'max torch32':>13}")
+    bad = []
+    for n in p64:
+        dh, d32 = (ph[n] - p64[n]).abs().flatten(), (p32[n] - p64[n]).abs().flatten()
+        qh, q32 = torch.quantile(dh, 0.999).item(), torch.quantile(d32, 0.999).item()
+        ulp = float(np.spacing(np.float32(p64[n].abs().max().item())))
+        print(f"{n:<18}{qh:12.3e}{q32:14.3e}{dh.max().item():12.3e}{d32.max().item():13.3e}")
+        if not qh <= max(8 * q32, ulp):
+            bad.append((n, "q999", qh, q32))
+        if not dh.max().item() <= displacement:
+            bad.append((n, "max", dh.max().item(), displacement))
+    print({k: (s_hip[k], s32[k], s64[k]) for k in s64})
+    assert not bad, bad
+    assert list(s_hip) == list(s64) and "mirror_loss" in s_hip
+    for k in ("value_loss", "surrogate_loss", "entropy", "kl", "mirror_loss"):
+        assert abs(s_hip[k] - s64[k]) <= 8 * abs(s32[k] - s64[k]) + 1e-6 * abs(s64[k]), (k, s_hip[k], s32[k], s64[k])
+    assert s_hip["mirror_loss"] > 0
+    assert s_hip["learning_rate"] == s64["learning_rate"] == s32["learning_rate"]
+    hip.close()
+
+
+def test_update_with_mirror_loss_is_deterministic(case):
+    import torch
+
+    from robot_lab_amd.ppo_hip import HipPPO
+
+    pol, st, _ = case
+    st32, tab, runs = _cast(st, torch.float32), _tables(3), []
+    for _ in range(2):
+        hip = HipPPO(copy.deepcopy(pol).to(DEV), symmetry=tab, mirror_loss=COEFF, data_augmentation=False)
+        stats = hip.update(st32, _gen())
+        runs.append([hip.flat(w).cpu() for w in ("parameters", "exp_avg", "exp_avg_sq")] + [torch.tensor(list(stats.values()), dtype=torch.float64)])
+        hip.close()
+    for x, y in zip(*runs):
+        assert torch.equal(x, y) and bool(torch.isfinite(x).all())
+
+
+def test_set_mirror_loss_refusals(case):
+    import torch
+
+    from robot_lab_amd.ppo_hip import HipPPO, RlPpoError
+    from robot_lab_amd.symmetry import SymmetryTables
+
+    pol, st, _ = case
+    tab = _tables(2)
+    # no symmetry
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=64)
+    with pytest.raises(RlPpoError, match="no symmetry is set"):
+        hip.set_mirror_loss(COEFF)
+    assert hip.mirror_loss is None
+    hip.close()
+    # the identity alone
+    ident = lambda dim: (np.arange(dim, dtype=np.int32)[None], np.ones((1, dim), dtype=np.float32))  # noqa: E731
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=64, symmetry=SymmetryTables(obs=ident(OD), critic=ident(CD), act=ident(A)))
+    with pytest.raises(RlPpoError, match="n_sym = 1"):
+        hip.set_mirror_loss(COEFF)
+    hip.close()
+    # the coefficient; a refused call leaves the learner as it was: no mirror loss, and the call that follows is the first
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=64, symmetry=tab)
+    for bad in (0.0, -0.5, float("nan")):
+        with pytest.raises(RlPpoError, match="finite and > 0"):
+            hip.set_mirror_loss(bad, False)
+        assert hip.mirror_loss is None and hip.data_augmentation is True and "mirror_loss" not in repr(hip)
+    hip.set_mirror_loss(COEFF, False)
+    assert hip.mirror_loss == COEFF and hip.data_augmentation is False
+    with pytest.raises(RlPpoError, match="already set"):  # twice
+        hip.set_mirror_loss(0.25, True)
+    assert hip.mirror_loss == COEFF and hip.data_augmentation is False
+    hip.close()
+    # late: after a mini-batch has run, the learner keeps computing what it computed
+    hip = HipPPO(copy.deepcopy(pol).to(DEV), max_rows_per_minibatch=64, symmetry=tab)
+    st32, idx = _cast(st, torch.float32), _perm()[:37]
+    g0 = hip.minibatch_grad(st32, idx).clone()
+    with pytest.raises(RlPpoError, match="refused after the first rl_ppo_minibatch_grad / rl_ppo_update"):
+        hip.set_mirror_loss(COEFF)
+    assert hip.mirror_loss is None and torch.equal(hip.minibatch_grad(st32, idx), g0)
+    hip.close()
+    # the Python class refuses what ppo.PPO refuses, before a handle exists
+    with pytest.raises(ValueError, match="mirror_loss needs symmetry="):
+        HipPPO(copy.deepcopy(pol).to(DEV), mirror_loss=COEFF)
+    with pytest.raises(ValueError, match="data_augmentation=False without mirror_loss"):
+        HipPPO(copy.deepcopy(pol).to(DEV), symmetry=tab, data_augmentation=False)
+
+
+@pytest.mark.parametrize("learner", ["hip", "torch"])
+def test_trainer_with_the_mirror_loss(learner):
+    import torch
+
+    from robot_lab_amd.env import ManagerBasedRLEnv
+    from robot_lab_amd.policy import MlpPolicy
+    from robot_lab_amd.ppo import Trainer
+
+    env = ManagerBasedRLEnv("RobotLab-Isaac-Velocity-Flat-Unitree-A1-v0", num_envs=256, seed=42, device=DEV)
+    tr = Trainer(env, seed=42, learner=learner, symmetry="lr", mirror_loss=0.5, data_augmentation=False)
+    assert tr.alg.mirror_loss == 0.5 and tr.alg.data_augmentation is False
+    assert "symmetry=SymmetryTables(n_sym=2, obs=45, critic=48, act=12), mirror_loss=0.5, data_augmentation=False" in repr(tr)
+    for _ in range(3):
+        out = tr.iterate()
+        assert all(np.isfinite(out[k]) for k in ("value_loss", "surrogate_loss", "entropy", "kl", "mirror_loss", "learning_rate", "mean_reward", "action_std")), out
+        assert out["mirror_loss"] >= 0
+    sd = tr.state_dict()
+    assert all(bool(torch.isfinite(v).all()) for v in sd.values())
+    pol = MlpPolicy.from_state_dict(sd, "actor", device=DEV)
+    obs = torch.randn(256, pol.in_dim, device=DEV)
+    torch.testing.assert_close(pol(obs).clone(), tr.actor(obs).clone(), rtol=0, atol=0)  # = the images the learner pushed
+    pol.close()
+    env.close()

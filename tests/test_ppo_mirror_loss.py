@@ -1,0 +1,175 @@
+"""rsl_rl's mirror loss in the torch learner, CPU tier: the rule of `ppo.PPO(symmetry=..., mirror_loss=c, data_augmentation=...)` against the
+UNCHANGED `PPO` plus the formula written out here,
+
+    L_mirror = 1 / ((n_sym - 1) n A) sum_{s >= 1} sum_i sum_k (actor(S_s^obs(o_i))[k] - S_s^act(actor(o_i)).detach()[k])^2
+
+on small fp64 networks, one epoch of one mini-batch without gradient clipping.  Without the augmentation the PPO part is the plain update
+on the stored rows; with it, the plain update on the materialised n_sym n rows (the construction of tests/test_ppo_symmetry.py).  The HIP
+learner's half is tests/test_gpu_ppo_hip_mirror.py.
+
+Agreement is held to fp64 round-off, measured in spacings of the tensor's largest entry: the two sides add the same ~10^3 terms per entry
+(up to n_sym * 24 rows times up to 16 units) in different orders, every addition can leave half a spacing of a partial sum, and partial sums
+exceed the (cancelling) result by a small factor - ULPS = 4096 spacings, 9e-13 relative, the 1e-12 of tests/test_ppo_symmetry.py."""
+import copy
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from robot_lab_amd.ppo import PPO, ActorCritic, gaussian_log_prob
+from robot_lab_amd.symmetry import SymmetryTables
+
+T, N, OD, CD, A = 3, 8, 11, 7, 5
+ROWS = T * N
+COEFF = 0.5
+ULPS = 4096
+KW = dict(num_learning_epochs=1, num_mini_batches=1, max_grad_norm=1e30)
+
+
+def _fake_storage(policy, seed=0):
+    """`_fake_storage` of tests/test_ppo.py in fp64 (action dimension 0 being positive is "good")"""
+    g = torch.Generator().manual_seed(seed)
+    obs, cobs = torch.randn(T, N, OD, generator=g, dtype=torch.float64), torch.randn(T, N, CD, generator=g, dtype=torch.float64)
+    with torch.no_grad():
+        mu, sd = policy.distribution(obs)
+        act = mu + sd * torch.randn(mu.shape, generator=g, dtype=torch.float64)
+        logp = gaussian_log_prob(act, mu, sd)
+        val = policy.critic(cobs).squeeze(-1)
+    adv = act[..., 0].clone()
+    adv = (adv - adv.mean()) / adv.std()
+    ret = val + adv
+    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
+                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
+
+
+def _random_table(rng, n_sym, dim):
+    """random signed permutations, row 0 the identity: arbitrary gathers, independent of symmetry.py's builders"""
+    perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
+    sign = np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
+    return perm, sign
+
+
+def _tables(n_sym, seed=7):
+    rng = np.random.default_rng(seed)
+    return SymmetryTables(obs=_random_table(rng, n_sym, OD), critic=_random_table(rng, n_sym, CD), act=_random_table(rng, n_sym, A))
+
+
+def _apply(table, s, x):
+    """S_s(x)[c] = sign[s][c] x[perm[s][c]]"""
+    perm, sign = torch.as_tensor(table[0].astype(np.int64)), torch.as_tensor(table[1].copy()).to(x.dtype)
+    return sign[s] * x[:, perm[s]]
+
+
+def _materialise(st, tab):
+    """the storage of n_sym * rows rows the augmentation is defined by (tests/test_ppo_symmetry.py), as a 1 x (n_sym rows) storage"""
+    ns = tab.n_sym
+    flat = lambda t: t.reshape(ROWS, -1)  # noqa: E731
+    out = types.SimpleNamespace(num_transitions_per_env=1, num_envs=ns * ROWS)
+    for k, table in (("observations", tab.obs), ("privileged_observations", tab.critic), ("actions", tab.act)):
+        setattr(out, k, torch.cat([_apply(table, s, flat(getattr(st, k))) for s in range(ns)], 0))
+    for k in ("values", "returns", "advantages", "actions_log_prob", "mu", "sigma"):
+        setattr(out, k, flat(getattr(st, k)).repeat(ns, 1))
+    for k, v in list(vars(out).items()):
+        if torch.is_tensor(v):
+            setattr(out, k, v.unsqueeze(0))
+    return out
+
+
+def _mirror_term(policy, st, tab):
+    """L_mirror from the formula, on a policy whose .grad fields are then those of L_mirror alone"""
+    obs = st.observations.reshape(ROWS, OD)
+    mu0 = policy.actor(obs)
+    total = 0.0
+    for s in range(1, tab.n_sym):
+        mu_s = policy.actor(_apply(tab.obs, s, obs))
+        tau_s = _apply(tab.act, s, mu0).detach()
+        total = total + ((mu_s - tau_s) ** 2).sum()
+    return total / ((tab.n_sym - 1) * ROWS * A)
+
+
+@pytest.fixture(scope="module")
+def case():
+    torch.manual_seed(0)
+    pol = ActorCritic(OD, CD, A, actor_hidden=(16, 8), critic_hidden=(16, 8)).double()
+    st = _fake_storage(pol)
+    g = torch.Generator().manual_seed(1)
+    with torch.no_grad():  # perturbed, so that the probability ratio of the stored rows is not 1
+        for p in pol.parameters():
+            p.add_(0.01 * torch.randn(p.shape, generator=g, dtype=torch.float64) * p.abs().mean())
+    return pol, st
+
+
+@pytest.mark.parametrize("n_sym", [2, 3])
+@pytest.mark.parametrize("augment", [False, True], ids=["mirror-only", "augmentation+mirror"])
+def test_rule_is_the_plain_update_plus_the_mirror_term(case, n_sym, augment):
+    pol, st = case
+    tab = _tables(n_sym)
+    alg = PPO(copy.deepcopy(pol), symmetry=tab, mirror_loss=COEFF, data_augmentation=augment, **KW)
+    stats = alg.update(st, torch.Generator().manual_seed(3))
+    # the PPO part: the unchanged learner, no symmetry keyword - on the stored rows, or on the materialised n_sym n rows
+    plain = PPO(copy.deepcopy(pol), **KW)
+    s_plain = plain.update(_materialise(st, tab) if augment else st, torch.Generator().manual_seed(4))
+    # the mirror part, from the formula
+    mir = copy.deepcopy(pol)
+    L = _mirror_term(mir, st, tab)
+    L.backward()
+    L = float(L.detach())
+    assert L > 0
+    seen_mirror_gradient = False
+    for (n, p), (_, q), (_, m) in zip(alg.policy.named_parameters(), plain.policy.named_parameters(), mir.named_parameters()):
+        gm = m.grad if m.grad is not None else torch.zeros_like(q.grad)  # (the critic and std take no part in L_mirror)
+        want = q.grad + COEFF * gm
+        scale = want.abs().max().item()
+        assert scale > 0
+        bound = ULPS * float(np.spacing(scale))
+        err = (p.grad - want).abs().max().item()
+        assert err <= bound, (n, err, bound)
+        if n.startswith("actor"):
+            assert (COEFF * gm).abs().max().item() > 1e3 * bound, n  # the term is visible: the test would notice its absence
+            seen_mirror_gradient = True
+    assert seen_mirror_gradient
+    assert abs(stats["mirror_loss"] - L) <= ULPS * float(np.spacing(L)), (stats["mirror_loss"], L)
+    for k in ("value_loss", "surrogate_loss", "entropy"):
+        assert abs(stats[k] - s_plain[k]) <= ULPS * float(np.spacing(abs(s_plain[k]))), (k, stats[k], s_plain[k])
+    if not augment:  # the KL statistic is that of the stored rows in both modes; the plain learner on the stored rows computes exactly it
+        assert abs(stats["kl"] - s_plain["kl"]) <= ULPS * float(np.spacing(s_plain["kl"]))
+    assert list(stats) == ["value_loss", "surrogate_loss", "entropy", "kl", "mirror_loss", "learning_rate"]
+
+
+def test_refusals(case):
+    pol, _ = case
+    tab = _tables(2)
+    ident = lambda dim: (np.arange(dim, dtype=np.int32)[None], np.ones((1, dim), dtype=np.float32))  # noqa: E731
+    one = SymmetryTables(obs=ident(OD), critic=ident(CD), act=ident(A))
+    with pytest.raises(ValueError, match="mirror_loss needs symmetry="):
+        PPO(copy.deepcopy(pol), mirror_loss=0.5)
+    with pytest.raises(ValueError, match="n_sym >= 2"):
+        PPO(copy.deepcopy(pol), symmetry=one, mirror_loss=0.5)
+    for bad in (0.0, -0.5, float("nan"), float("inf"), True, "0.5"):
+        with pytest.raises(ValueError, match="finite coefficient > 0"):
+            PPO(copy.deepcopy(pol), symmetry=tab, mirror_loss=bad)
+    with pytest.raises(ValueError, match="data_augmentation=False without mirror_loss"):
+        PPO(copy.deepcopy(pol), symmetry=tab, data_augmentation=False)
+    alg = PPO(copy.deepcopy(pol), symmetry=tab, mirror_loss=0.25, data_augmentation=False)
+    assert alg.mirror_loss == 0.25 and alg.data_augmentation is False
+
+
+def test_key_is_absent_when_the_option_is_off(case):
+    pol, st = case
+    for kw in ({}, dict(symmetry=_tables(2)), dict(symmetry=_tables(2), data_augmentation=True)):
+        alg = PPO(copy.deepcopy(pol), **KW, **kw)
+        assert alg.mirror_loss is None
+        assert list(alg.update(st, torch.Generator().manual_seed(3))) == ["value_loss", "surrogate_loss", "entropy", "kl", "learning_rate"]
+
+
+def test_repr_suffix():
+    """what `HipPPO` and `Trainer` print after the symmetry"""
+    from robot_lab_amd.ppo import mirror_repr
+
+    learner = types.SimpleNamespace(mirror_loss=0.5, data_augmentation=False)
+    assert mirror_repr(learner) == ", mirror_loss=0.5, data_augmentation=False"
+    learner.data_augmentation = True
+    assert mirror_repr(learner) == ", mirror_loss=0.5"
+    learner.mirror_loss = None
+    assert mirror_repr(learner) == ""

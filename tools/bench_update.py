@@ -15,7 +15,11 @@ both learners with the SAME tables, every setting on the same collected batch in
 `symmetry.tables_for_env`; for a robot it has none for (the humanoids) the timing uses random signed permutations with as many copies
 ("tables": "random" in the output) - the cost of the gather does not depend on which permutation it is.  Reported beside the times: the HIP
 time over n_sym x the HIP time of the "off" setting of the same run, when "off" is among the settings.
-    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...]"""
+
+`--mirror-loss C`: every `--symmetry` entry other than "off" is timed three times - the augmentation alone, the augmentation + the mirror
+loss with coefficient C, the mirror loss alone (`data_augmentation=False`: only the actor sees the copies) - and each line carries
+`hip_over_off`, the HIP time as a multiple of the "off" setting's.
+    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...] [--mirror-loss C]"""
 import argparse
 import copy
 import json
@@ -33,13 +37,14 @@ from robot_lab_amd.ppo_hip import HipPPO  # noqa: E402
 from robot_lab_amd.symmetry import SymmetryTables, parse_mirrors, tables_for_env  # noqa: E402
 
 
-def update_flops(alg: HipPPO, rows: int) -> float:
-    """2 flops per multiply-add x (forward + dW for every layer, dX for every layer but the first) x rows x epochs"""
-    macs = 0
-    for dims in (alg.actor_dims, alg.critic_dims):
-        for l in range(len(dims) - 1):
-            macs += dims[l] * dims[l + 1] * (3 if l > 0 else 2)
-    return 2.0 * macs * rows * alg.num_learning_epochs
+def update_flops(alg: HipPPO, rows: int, n_sym: int = 1) -> float:
+    """2 flops per multiply-add x (forward + dW for every layer, dX for every layer but the first) x rows x epochs; the actor's rows are the
+    n_sym copies, the critic's too unless the learner runs the mirror loss without the augmentation"""
+    flops = 0.0
+    for dims, copies in ((alg.actor_dims, n_sym), (alg.critic_dims, n_sym if alg.data_augmentation else 1)):
+        macs = sum(dims[l] * dims[l + 1] * (3 if l > 0 else 2) for l in range(len(dims) - 1))
+        flops += 2.0 * macs * rows * copies * alg.num_learning_epochs
+    return flops
 
 
 def tables(env, spec, dims):
@@ -61,7 +66,7 @@ def tables(env, spec, dims):
         return SymmetryTables(obs=rnd(dims[0]), critic=rnd(dims[1]), act=rnd(dims[2])), "random"
 
 
-def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42):
+def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_loss=None):
     env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
     tr = Trainer(env, seed=seed)
     tr.collector.collect()
@@ -69,20 +74,28 @@ def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42):
     out, hip_off = [], None
     for spec in symmetry:
         tab, kind = tables(env, spec, (tr.storage.observations.shape[-1], tr.storage.privileged_observations.shape[-1], env.num_actions))
-        res = bench_one(tr, tab, repeat, warmup, seed)
-        res = dict(task=task, num_envs=num_envs, symmetry=spec, tables=kind, n_sym=tab.n_sym if tab else 1, **res)
-        if spec == "off":
-            hip_off = res["hip"]["median_ms"]
-        elif hip_off:
-            res["hip_over_n_sym_x_off"] = res["hip"]["median_ms"] / (res["n_sym"] * hip_off)
-        out.append(res)
+        settings = [{}]  # keywords of both learners beside symmetry=
+        if tab is not None and mirror_loss is not None:
+            settings += [dict(mirror_loss=mirror_loss), dict(mirror_loss=mirror_loss, data_augmentation=False)]
+        for kw in settings:
+            res = bench_one(tr, tab, repeat, warmup, seed, **kw)
+            res = dict(task=task, num_envs=num_envs, symmetry=spec, tables=kind, n_sym=tab.n_sym if tab else 1, **res)
+            if mirror_loss is not None:
+                res.update(mirror_loss=kw.get("mirror_loss"), data_augmentation=kw.get("data_augmentation", True))
+            if spec == "off":
+                hip_off = res["hip"]["median_ms"]
+            elif hip_off:
+                res["hip_over_n_sym_x_off"] = res["hip"]["median_ms"] / (res["n_sym"] * hip_off)
+                if mirror_loss is not None:
+                    res["hip_over_off"] = res["hip"]["median_ms"] / hip_off
+            out.append(res)
     env.close()
     return out
 
 
-def bench_one(tr, tab, repeat, warmup, seed):
+def bench_one(tr, tab, repeat, warmup, seed, **kw):
     st = tr.storage
-    learners = {"torch": PPO(copy.deepcopy(tr.policy), symmetry=tab), "hip": HipPPO(copy.deepcopy(tr.policy), symmetry=tab)}
+    learners = {"torch": PPO(copy.deepcopy(tr.policy), symmetry=tab, **kw), "hip": HipPPO(copy.deepcopy(tr.policy), symmetry=tab, **kw)}
     gens = {k: torch.Generator(device="cuda:0").manual_seed(seed) for k in learners}
     times = {k: [] for k in learners}
     for it in range(warmup + repeat):
@@ -97,7 +110,7 @@ def bench_one(tr, tab, repeat, warmup, seed):
                 times[k].append(t0.elapsed_time(t1))
             assert all(v == v for v in out.values()), (k, out)  # no NaN
     rows = st.num_transitions_per_env * st.num_envs
-    flops = update_flops(learners["hip"], rows) * (tab.n_sym if tab else 1)
+    flops = update_flops(learners["hip"], rows, tab.n_sym if tab else 1)
     res = dict(rows=rows, repeat=repeat, warmup=warmup, update_gflop=flops / 1e9)
     for k, t in times.items():
         med = statistics.median(t)
@@ -114,6 +127,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--symmetry", nargs="+", default=["off"], help="settings to time, each \"off\" or mirrors (lr | fb | lr,fb)")
+    ap.add_argument("--mirror-loss", type=float, default=None, metavar="C", help="also time every symmetry setting with the mirror loss, with and without the augmentation")
     a = ap.parse_args()
     for spec in a.symmetry:
         if spec != "off":
@@ -121,7 +135,7 @@ def main():
     if len(a.num_envs) != len(a.task):
         ap.error("one --num-envs per --task")
     for task, n in zip(a.task, a.num_envs):
-        for res in bench(task, n, a.repeat, a.warmup, a.symmetry):
+        for res in bench(task, n, a.repeat, a.warmup, a.symmetry, mirror_loss=a.mirror_loss):
             print(json.dumps(res), flush=True)
 
 

@@ -10,8 +10,10 @@ rsl-rl-lib, which is not installable here.  A robot that learns to follow veloci
 evidence that observations, actions, actuators, contacts, rewards, resets and curricula hang together - something no per-step
 parity test against our own oracle can show.
 `--learner hip` runs the update as HIP kernels instead (robot_lab_amd/ppo_hip.py, csrc/rl_ppo.hip) and pushes with rl_mlp_set_weights_device.
-`--symmetry lr` (or `lr,fb`) turns on symmetry data augmentation inside the update of either learner (`Trainer(symmetry=...)`).
-    python tools/train_demo.py [--task ID] [--num-envs N] [--iterations K] [--learner torch|hip] [--symmetry lr|fb|lr,fb] [--out DIR]"""
+`--symmetry lr` (or `lr,fb`) turns on symmetry data augmentation inside the update of either learner (`Trainer(symmetry=...)`);
+`--mirror-loss C` adds rsl_rl's mirror loss with coefficient C on the same tables, `--no-data-augmentation` keeps the mirror loss alone.
+    python tools/train_demo.py [--task ID] [--num-envs N] [--iterations K] [--learner torch|hip] [--symmetry lr|fb|lr,fb] [--mirror-loss C]
+                               [--no-data-augmentation] [--out DIR]"""
 import argparse
 import json
 import os
@@ -33,10 +35,14 @@ def main():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--learner", choices=("torch", "hip"), default="torch", help="torch: autograd (robot_lab_amd/ppo.py); hip: the HIP learner (robot_lab_amd/ppo_hip.py)")
     ap.add_argument("--symmetry", default=None, help="mirrors of the symmetry data augmentation inside the update: lr, fb or lr,fb (default: none)")
+    ap.add_argument("--mirror-loss", type=float, default=None, metavar="C", help="coefficient of the mirror loss on the --symmetry tables (default: off)")
+    ap.add_argument("--no-data-augmentation", action="store_true", help="with --mirror-loss: the PPO terms stay on the stored rows")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--also-terminate-on", default="", help="DIAGNOSTIC, not the reference's cfg: regex of body names added to the illegal-contact termination")
     a = ap.parse_args()
+    if not a.symmetry and (a.mirror_loss is not None or a.no_data_augmentation):
+        ap.error("--mirror-loss / --no-data-augmentation need --symmetry")
     if a.also_terminate_on:
         import re
 
@@ -52,7 +58,8 @@ def main():
     else:
         env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=a.seed, device="cuda:0")
     print(env, flush=True)  # (names the step kernel: specialised on the task, or the interpreter)
-    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry)
+    mirror = dict(mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation) if a.symmetry else {}
+    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror)
     print(tr, flush=True)
     # init_at_random_ep_len=True (train.py:224): the first time-outs are spread over an episode length
     env.episode_length_buf = torch.randint(0, env.max_episode_length, (a.num_envs,), generator=torch.Generator().manual_seed(a.seed))
@@ -92,7 +99,7 @@ def main():
                   f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
     wall = time.perf_counter() - t_start
     n_steps = a.iterations * st.num_transitions_per_env * a.num_envs
-    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, step_kernel=env.step_kernel, num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
+    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
                    collect_ms_per_iteration=1e3 * t_collect / a.iterations, update_ms_per_iteration=1e3 * t_update / a.iterations,
                    first=log[0], last=log[-1])
     print(json.dumps({k: v for k, v in summary.items() if k not in ("first", "last")}))
