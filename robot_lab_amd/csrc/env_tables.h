@@ -34,7 +34,7 @@ constexpr int MAX_NBS = 9;  // body slots per lane: 0 = a trunk-link body (or em
 // legs with rotated hip frames, two empty limbs (round 5; it ran on the trunk + limbs instance before: 185 us at 2048 envs).
 template <int CL_, int NW_, int SPL_, int NBS_, int M0_ = 0, int RP_ = 0>
 struct Topo {
-  static constexpr int CL = CL_, NW = NW_, SPL = SPL_, NBS = NBS_, JX = CL_ + NW_, NB = 6 + NW_, M0 = M0_;
+  static constexpr int CL = CL_, NW = NW_, SPL = SPL_, NBS = NBS_, JX = CL_ + NW_, NB = 6 + NW_, M0 = M0_, RP = RP_;
   static_assert(M0_ == 0 || NW_ == 0, "merged base share: quadruped instances only");
   static constexpr bool ROT = NW_ > 0 || RP_ != 0;  // joint frames may be rotated w.r.t. the parent link (URDF joint rpy)
   static constexpr bool PAD = NW_ > 0 || RP_ != 0;  // a limb may have fewer than CL joints: joint_id -1 = inert padding (identity row in the elimination)
@@ -47,6 +47,45 @@ using TopoQuad4M = Topo<4, 0, 3, 6, 1>;  // Go2W and the other wheeled quadruped
 using TopoQuad4R = Topo<4, 0, 3, 6, 0, 1>;  // <= 4-joint limbs with rotated joint frames and / or limbs of unequal length (DDT Tita)
 using TopoG1 = Topo<7, 3, 4, 9>;     // G1 29-DoF
 using TopoGR = Topo<7, 6, 4, 9>;     // FFTAI GR1T1 / GR1T2 (32 DoF): a six-joint spine - waist, then head - with the arms leaving it at depth 3
+// The lane-program instances, written down ONCE: every host dispatch (table image, LDS need, kernel launch, the emulator's run, the
+// spec generator's Topo name) goes through visit_instance below.  Key of an instance = CL + 100 merged + 200 six-joint trunk + 400 rot / pad;
+// the codes of RL_ENV_ONLY / RL_EMU_ONLY (tools/build_variant.sh, tools/kbuild.sh, tools/ablate.sh, bench.py) are key * 10 + lanes per limb.
+#define RL_INSTANCE_LIST(X) X(TopoQuad3) X(TopoQuad4) X(TopoQuad4M) X(TopoQuad4R) X(TopoG1) X(TopoGR)
+constexpr int instance_key(int CL, int NW, bool merged, bool rotpad) { return CL + (merged ? 100 : 0) + (NW > 3 ? 200 : 0) + (rotpad ? 400 : 0); }
+template <class TP>
+constexpr int instance_key() { return instance_key(TP::CL, TP::NW, TP::M0 != 0, TP::RP != 0); }
+static_assert(instance_key<TopoQuad3>() == 3 && instance_key<TopoQuad4>() == 4 && instance_key<TopoQuad4M>() == 104 && instance_key<TopoQuad4R>() == 404 &&
+              instance_key<TopoG1>() == 7 && instance_key<TopoGR>() == 207, "instance keys are part of the build-time switches");
+// lane mappings (SUB lanes per limb) of an instance: quadrupeds 1, 2, 4; trunk + limbs 4, 8 - and 1 on the CPU lane emulator only (EMU):
+// 64 limbs per wavefront would need more LDS than a CU has
+template <class TP, int SUB, bool EMU = false>
+constexpr bool instance_has_sub() { return TP::NW == 0 ? (SUB == 1 || SUB == 2 || SUB == 4) : (SUB == 4 || SUB == 8 || (EMU && SUB == 1)); }
+template <class TP>
+struct TopoTag { using type = TP; const char* name; };
+template <int SUB>
+struct SubTag { static constexpr int value = SUB; };
+// f(TopoTag<TP>) for the instance of a key; false: there is none
+template <class F>
+inline bool visit_instance(int key, F&& f) {
+#define RL_INSTANCE_VISIT(TP) if (key == instance_key<TP>()) { f(TopoTag<TP>{#TP}); return true; }
+  RL_INSTANCE_LIST(RL_INSTANCE_VISIT)
+#undef RL_INSTANCE_VISIT
+  return false;
+}
+// f(TopoTag<TP>, SubTag<SUB>) for the instance of a key in lane mapping `sub`; false: no such instance, or it has no such mapping
+template <bool EMU = false, class F>
+inline bool visit_instance(int key, int sub, F&& f) {
+  bool hit = false;
+  visit_instance(key, [&](auto tp) {
+    using TP = typename decltype(tp)::type;
+    auto one = [&](auto s) {
+      if constexpr (instance_has_sub<TP, decltype(s)::value, EMU>())
+        if (sub == decltype(s)::value) { f(tp, s); hit = true; }
+    };
+    one(SubTag<1>{}); one(SubTag<2>{}); one(SubTag<4>{}); one(SubTag<8>{});
+  });
+  return hit;
+}
 constexpr int MAX_T = 40;   // reward terms
 constexpr int MAX_OBS = 12;
 constexpr int MAX_BASE_BODIES = 4;
@@ -260,6 +299,9 @@ struct TablesBody : TaskTab {
 template <class TP>
 struct TablesT : TablesBody<TP>, SelfTail<(TP::NW > 0)> {};  // (the tail sits behind rew[] in the image: never staged)
 using Tables = TablesT<TopoMax>;  // host side / export-import kernels; env kernels read the packed TablesT<TP>
+inline int instance_key(const TaskTab& T) { return instance_key(T.CL, T.NW, T.merged != 0, T.rotpad != 0); }
+template <class F>
+inline bool visit_instance(const TaskTab& T, F&& f) { return visit_instance(instance_key(T), static_cast<F&&>(f)); }
 
 // host: unpacked -> the instance's compact layout (trunk joints already sit at [CL, CL + NW) of the joint arrays)
 template <class TP>

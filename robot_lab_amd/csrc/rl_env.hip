@@ -119,8 +119,7 @@ struct Backend {
     const int ept = envs_per_wave(T, Npad);
     if (configure(T)) return -1;
     const size_t tb = staged_bytes(T), lds4 = tb + 4 * (lds_bytes - tb);
-    const int tiles = Npad / ept;
-    const bool four = (T.NW == 0 || sub == 8) && cfg.wg_waves == 4 && (tiles >= 4 * n_cu || cfg.wg_force) && lds4 <= 160 * 1024;  // launch_cl
+    const bool four = four_wave_workgroup(cfg, T.NW, sub, Npad / ept, lds_bytes, tb);
     out[0] = sub; out[1] = four ? 4 : 1; out[2] = (int32_t)lds_bytes; out[3] = (int32_t)(four ? lds4 : lds_bytes);
     return 0;
   }
@@ -163,7 +162,7 @@ struct Backend {
       // 16-lane one (measured: profiles/r04*_g1_sub8*.txt)
       sub = 4;
       if (T.sub8_ok) {
-        const size_t n4 = T.NW > 3 ? lds_need<TopoGR, 4>(T) : lds_need<TopoG1, 4>(T), n8 = T.NW > 3 ? lds_need<TopoGR, 8>(T) : lds_need<TopoG1, 8>(T);
+        const size_t n4 = lds_need(T, 4), n8 = lds_need(T, 8);
         const size_t tb = staged_bytes(T);
         const double slots4 = (double)n_cu * (double)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / n4));
         const double slots8 = (double)n_cu * (double)((tb + 4 * (n8 - tb) <= 160 * 1024) ? 4 : std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / n8)));
@@ -176,15 +175,8 @@ struct Backend {
       }
     } else if (T.NW == 0) {
       const size_t tb = staged_bytes(T);
-      size_t need[3] = {0, 0, 0};  // LDS of a single-wavefront workgroup, mappings 4 / 2 / 1
-      switch (T.CL + (T.merged ? 100 : 0) + (T.rotpad ? 400 : 0)) {
-        case 404: need[0] = lds_need<TopoQuad4R, 4>(T); need[1] = lds_need<TopoQuad4R, 2>(T); need[2] = lds_need<TopoQuad4R, 1>(T); break;
-        case 3: need[0] = lds_need<TopoQuad3, 4>(T); need[1] = lds_need<TopoQuad3, 2>(T); need[2] = lds_need<TopoQuad3, 1>(T); break;
-        case 4: need[0] = lds_need<TopoQuad4, 4>(T); need[1] = lds_need<TopoQuad4, 2>(T); need[2] = lds_need<TopoQuad4, 1>(T); break;
-        case 104: need[0] = lds_need<TopoQuad4M, 4>(T); need[1] = lds_need<TopoQuad4M, 2>(T); need[2] = lds_need<TopoQuad4M, 1>(T); break;
-        default: break;
-      }
       const int subs[3] = {4, 2, 1};
+      const size_t need[3] = {lds_need(T, 4), lds_need(T, 2), lds_need(T, 1)};  // LDS of a single-wavefront workgroup (0: no such instance)
       const double cost[3] = {1.0, 1.45, 2.29};  // (one lane per limb: 97.6 us since its state tiles are addressed as buffers, profiles/r04i_state_buf_ab.txt)
       double best = 0.0, t[3] = {0.0, 0.0, 0.0};
       for (int i = 0; i < 3; ++i) {
@@ -209,30 +201,18 @@ struct Backend {
     const LdsPlan P = lds_plan<TP, SUB>(T.policy_dim, T.critic_dim, direct_group(T, 0), direct_group(T, 1), T.D, T.n_bodies, T.rew_ext_mask, T.n_rewards);
     return staged_bytes(T) + (size_t)P.words * 4;
   }
+  static size_t lds_need(const Tables& T, int sub_) {  // ... of the task's instance in lane mapping sub_; 0: the instance has no such mapping
+    size_t n = 0;
+    visit_instance(instance_key(T), sub_, [&](auto tp, auto s) { n = lds_need<typename decltype(tp)::type, decltype(s)::value>(T); });
+    return n;
+  }
   int configure(const Tables& T) {
-    const int key = (T.CL + (T.merged ? 100 : 0) + (T.NW > 3 ? 200 : 0) + (T.rotpad ? 400 : 0)) * 10 + sub;
-    switch (key) {
-      case 31: lds_bytes = lds_need<TopoQuad3, 1>(T); break;
-      case 32: lds_bytes = lds_need<TopoQuad3, 2>(T); break;
-      case 34: lds_bytes = lds_need<TopoQuad3, 4>(T); break;
-      case 41: lds_bytes = lds_need<TopoQuad4, 1>(T); break;
-      case 42: lds_bytes = lds_need<TopoQuad4, 2>(T); break;
-      case 44: lds_bytes = lds_need<TopoQuad4, 4>(T); break;
-      case 1041: lds_bytes = lds_need<TopoQuad4M, 1>(T); break;
-      case 1042: lds_bytes = lds_need<TopoQuad4M, 2>(T); break;
-      case 1044: lds_bytes = lds_need<TopoQuad4M, 4>(T); break;
-      case 4041: lds_bytes = lds_need<TopoQuad4R, 1>(T); break;
-      case 4042: lds_bytes = lds_need<TopoQuad4R, 2>(T); break;
-      case 4044: lds_bytes = lds_need<TopoQuad4R, 4>(T); break;
-      case 71:  // 64 limbs per wavefront: 115 KB of limb-shared words + 30 KB of sensor rows.  The CPU lane emulator runs it (tests/emu); no kernel is built for it
-        err = "the one-lane-per-limb mapping (RL_ENV_SUB=1) of the trunk + limbs instance needs more LDS than a CU has";
-        return -1;
-      case 74: lds_bytes = lds_need<TopoG1, 4>(T); break;
-      case 78: lds_bytes = lds_need<TopoG1, 8>(T); break;
-      case 2078: lds_bytes = lds_need<TopoGR, 8>(T); break;
-      case 2071: err = "the one-lane-per-limb mapping (RL_ENV_SUB=1) of the trunk + limbs instance needs more LDS than a CU has"; return -1;
-      case 2074: lds_bytes = lds_need<TopoGR, 4>(T); break;
-      default: err = "no lane-program instance for chain length " + std::to_string(T.CL); return -1;
+    lds_bytes = lds_need(T, sub);
+    if (lds_bytes == 0) {
+      // 64 limbs per wavefront: 115 KB of limb-shared words + 30 KB of sensor rows.  The CPU lane emulator runs that mapping (tests/emu); no kernel is built for it
+      if (visit_instance<true>(instance_key(T), sub, [](auto, auto) {})) err = "the one-lane-per-limb mapping (RL_ENV_SUB=1) of the trunk + limbs instance needs more LDS than a CU has";
+      else err = "no lane-program instance for chain length " + std::to_string(T.CL);
+      return -1;
     }
     if (std::getenv("RL_ENV_DEBUG")) fprintf(stderr, "rl_env: %zu B of LDS per single-wavefront workgroup (%zu fit a CU)\n", lds_bytes, (size_t)(160 * 1024) / lds_bytes);
     if (lds_bytes > 160 * 1024) {
@@ -252,7 +232,7 @@ struct Backend {
       }
     return 0;
   }
-  int launch(const KState& S, const void* T, int CL, void* stream) {  // CL: chain length, + 100 for a merged instance, + 400 for the rot / pad quadruped; S.mode: what to run
+  int launch(const KState& S, const void* T, int inst, void* stream) {  // inst: the instance key (env_tables.h instance_key); S.mode: what to run
     hipStream_t st = (hipStream_t)stream;
     if (spec_id >= 1000 && plugin_launch && S.mode == KMODE_STEP) {  // (a plugin built for another lane mapping answers -2: the interpreter below)
       const int rc = plugin_launch(&cfg, &S, T, sub, lds_bytes, stream);
@@ -268,38 +248,15 @@ struct Backend {
       }
       if (rc != -2) return check((hipError_t)rc);
     }
-    // RL_ENV_ONLY=<CL * 10 + SUB> (e.g. 34; 1044: merged): build that one instance only - kernel experiments compile in 15 s instead of 80
-#ifndef RL_ENV_ONLY
-#define RL_ENV_ONLY 0
-#endif
-    const std::string missing = "this build does not carry the lane-program instance for chain length " + std::to_string(CL) + " / " + std::to_string(sub) + " lanes per limb";
-    if (sub != 4) {  // the 8- and 4-lane mappings: kernels of their own translation units (rl_env_sub.inl)
-      const int rc = sub == 8 ? rl_env_launch_sub8(&cfg, &S, T, CL, lds_bytes, stream)
-                              : (sub == 2 ? rl_env_launch_sub2(&cfg, &S, T, CL, lds_bytes, stream) : rl_env_launch_sub1(&cfg, &S, T, CL, lds_bytes, stream));
-      if (rc == -2) { err = missing; return -1; }
-      return check((hipError_t)rc);
+    // the interpreter's kernels (rl_env_kernels.h launch_inst): 16 lanes per env here, the other mappings in translation units of their own (rl_env_sub.inl)
+    const int rc = sub == 4 ? launch_inst<4>(cfg, S, T, inst, lds_bytes, st)
+                            : (sub == 8 ? rl_env_launch_sub8(&cfg, &S, T, inst, lds_bytes, stream)
+                                        : (sub == 2 ? rl_env_launch_sub2(&cfg, &S, T, inst, lds_bytes, stream) : rl_env_launch_sub1(&cfg, &S, T, inst, lds_bytes, stream)));
+    if (rc == -2) {
+      err = "this build does not carry the lane-program instance for chain length " + std::to_string(inst) + " / " + std::to_string(sub) + " lanes per limb";
+      return -1;
     }
-    switch (CL) {
-#if RL_ENV_ONLY == 0 || RL_ENV_ONLY == 34
-      case 3: return check(launch_cl<TopoQuad3, 4>(cfg, S, T, lds_bytes, st));
-#endif
-#if RL_ENV_ONLY == 0 || RL_ENV_ONLY == 44
-      case 4: return check(launch_cl<TopoQuad4, 4>(cfg, S, T, lds_bytes, st));
-#endif
-#if RL_ENV_ONLY == 0 || RL_ENV_ONLY == 1044
-      case 104: return check(launch_cl<TopoQuad4M, 4>(cfg, S, T, lds_bytes, st));
-#endif
-#if RL_ENV_ONLY == 0 || RL_ENV_ONLY == 4044
-      case 404: return check(launch_cl<TopoQuad4R, 4>(cfg, S, T, lds_bytes, st));
-#endif
-#if RL_ENV_ONLY == 0 || RL_ENV_ONLY == 74
-      case 7: return check(launch_cl<TopoG1, 4>(cfg, S, T, lds_bytes, st));
-#endif
-#if RL_ENV_ONLY == 0 || RL_ENV_ONLY == 2074
-      case 207: return check(launch_cl<TopoGR, 4>(cfg, S, T, lds_bytes, st));
-#endif
-      default: err = missing; return -1;
-    }
+    return check((hipError_t)rc);
   }
   int launch_export(const KState& S, const Tables* T, const AosPtrs& A, void* stream) {
     hipLaunchKernelGGL(export_kernel, dim3((S.Npad + 63) / 64), dim3(64), 0, (hipStream_t)stream, S, T, A);

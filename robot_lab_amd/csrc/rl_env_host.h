@@ -5,6 +5,7 @@
 #pragma once
 #include <math.h>
 #include <stdio.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <string>
@@ -75,21 +76,37 @@ inline int topo_shape(const rl_model_desc& m, int& CL, int& NW, int& SPL, int& N
   return 0;
 }
 
-inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_lane, std::vector<int>& body_slot, std::vector<int>& link_lane_out,
-                        std::vector<int>& link_pos_out, bool merge = false) {
-  memset(&T, 0, sizeof(T));
-  const rl_model_desc& m = d.model;
-  int CL, NW, SPL, NBS, rotpad;
-  if (topo_shape(m, CL, NW, SPL, NBS, rotpad)) return -1;
-  const int NGRP = CL + 1;
-  if (merge && !(NW == 0 && CL == 4 && !rotpad)) return fail("merged base share: 4-joint quadruped limbs (same length, unrotated joint frames) only");
-  T.CL = CL; T.NW = NW; T.SPL = SPL; T.NBS = NBS; T.nw_used = m.num_trunk; T.merged = merge ? 1 : 0; T.rotpad = rotpad;
+// What the passes of build_tables share: the descriptor, the tables under construction, the shape of the instance, and what a pass leaves
+// for a later one.  The passes run in the order they are declared in; each returns 0, or -1 with last_error() set.
+struct TableBuild {
+  const rl_env_desc& d;
+  const rl_model_desc& m;
+  Tables& T;
+  std::vector<int>&body_lane, &body_slot;
+  std::vector<int>& link_k;  // limb links: lane; trunk links: -1
+  std::vector<int>& link_j;  // limb links: position in the chain; trunk links: trunk depth (0 = base)
+  const bool merge;
+  int CL, NW, SPL, NBS, NGRP;  // topo_shape
+  std::vector<int> nsph;        // collision spheres of a body
+  int next_slot[NLANE];         // first free body slot of a lane
+  int fill[NLANE][MAX_NGRP];    // sphere slots in use, per lane and link group
+  int topology();       // trunk and limb chains, joints
+  int self_collision(); // capsules and capsule pairs
+  int body_slots();     // bodies -> lane slots
+  int sphere_slots();   // spheres -> lane / group / slot
+  int sublane_slots();  // own_slot, own_slot2, sub8_ok
+  int addressed();      // bodies the events / the scanner address, slot_valid
+  int scalars();        // sim / terrain / command scalars
+  int observations();   // observation groups
+  int rewards();        // reward terms and their evaluation schedule
+  int terminations();   // terminations, events, the RL_ENV_TERMS / RL_ENV_INTERVALS ablation switches
+};
+
+inline int TableBuild::topology() {
   T.D = m.num_dof;
   T.n_bodies = m.num_bodies;
   body_lane.assign(m.num_bodies, -1);
   body_slot.assign(m.num_bodies, -1);
-  std::vector<int>& link_k = link_lane_out;   // limb links: lane; trunk links: -1
-  std::vector<int>& link_j = link_pos_out;    // limb links: position in the chain; trunk links: trunk depth (0 = base)
   link_k.assign(m.num_links, -2);
   link_j.assign(m.num_links, -1);
   link_k[0] = -1; link_j[0] = 0;
@@ -153,6 +170,9 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
   }
   for (int l = 0; l < m.num_links; ++l)
     if (link_k[l] == -2) return fail("link " + std::to_string(l) + " belongs to neither the trunk nor a limb chain");
+  return 0;
+}
+inline int TableBuild::self_collision() {
   // self-collision: capsules and capsule pairs dealt to the env's 16 virtual lanes (env_tables.h SelfLaneTab)
   for (int v = 0; v < SELF_CAPS; ++v) {
     SelfLaneTab& sl = T.self_lane[v];
@@ -194,12 +214,15 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
       T.self_lane[p % SELF_CAPS].pair[p / SELF_CAPS] = a | b << 4 | cap_k[a] << 8 | cap_g[a] << 11 | cap_k[b] << 15 | cap_g[b] << 18;
     }
   }
+  return 0;
+}
+inline int TableBuild::body_slots() {
   // bodies -> lane slots.  Trunk-link bodies with collision spheres: slot 0 of a lane whose group 0 rides
   // on that trunk link; limb bodies: slots 1.. of their lane; sphere-less trunk bodies: any free slot.
-  std::vector<int> nsph(m.num_bodies, 0);
+  nsph.assign(m.num_bodies, 0);
   for (int g = 0; g < m.num_spheres; ++g) nsph[m.sphere_body[g]]++;
   int n_base_bodies = 0;
-  int next_slot[NLANE] = {1, 1, 1, 1};
+  for (int k = 0; k < NLANE; ++k) next_slot[k] = 1;
   std::vector<int> deferred;
   for (int b = 0; b < m.num_bodies; ++b) {
     int link = m.body_link[b];
@@ -240,6 +263,9 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
     body_lane[b] = k; body_slot[b] = s;
   }
   T.n_base_bodies = n_base_bodies;
+  return 0;
+}
+inline int TableBuild::sphere_slots() {
   // spheres -> lane / group / slot.  A trunk body with more spheres than its lane has slots also uses the lanes
   // riding on the same trunk link that own no trunk body: first every such body reserves the lanes it needs
   // (MagicLab Dog-W: 6-sphere base + 4-sphere head), then the lanes still free go to the first of them in body
@@ -247,7 +273,6 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
   // Limb spheres first: a merged instance (Topo<..., M0 = 1>) hosts the lane's share of the trunk link's spheres in the sphere
   // slots its limb link groups leave free, so a lane's room for trunk spheres is known only then.  When the trunk spheres do not
   // fit, the caller builds the tables again unmerged.
-  int fill[NLANE][MAX_NGRP];
   memset(fill, 0, sizeof(fill));
   auto put_sphere = [&](int k, int grp, int g, int slot) {
     LaneTab& L = T.lane[k];
@@ -308,6 +333,9 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
     const int s = put_sphere(k, grp, g, 0);
     if (merge) T.lane[k].sph_base_mask |= 1u << (grp * SPL + s);
   }
+  return 0;
+}
+inline int TableBuild::sublane_slots() {
   // 16-lanes-per-env mapping: body slots each sub-lane updates (the slots of the link groups it evaluates)
   for (int k = 0; k < NLANE; ++k) {
     LaneTab& L = T.lane[k];
@@ -350,6 +378,9 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
       }
     }
   }
+  return 0;
+}
+inline int TableBuild::addressed() {
   // bodies the events / the scanner address
   {
     const int wl = m.body_link[d.task.base_body], sl = m.body_link[d.task.scan_body];
@@ -365,6 +396,9 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
     for (int g = 0; g < NGRP; ++g)
       for (int s2 = 0; s2 < SPL; ++s2)
         if (T.lane[k].sph_r[g][s2] > 0.f) T.slot_valid |= 1u << (g * SPL + s2);
+  return 0;
+}
+inline int TableBuild::scalars() {
   // sim / terrain / task scalars
   const rl_sim_desc& s = d.sim;
   T.dt = s.dt; T.decimation = s.decimation; T.gravity = s.gravity; T.contact_k = s.contact_k; T.contact_c = s.contact_c;
@@ -384,6 +418,10 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
   T.cur_lin = t.cur_cmd_lin; T.cur_ang = t.cur_cmd_ang; T.cur_lin_term = t.cur_cmd_lin_term; T.cur_ang_term = t.cur_cmd_ang_term;
   if ((t.cur_cmd_lin && (t.cur_cmd_lin_term < 0 || t.cur_cmd_lin_term >= t.n_rewards)) || (t.cur_cmd_ang && (t.cur_cmd_ang_term < 0 || t.cur_cmd_ang_term >= t.n_rewards)))
     return fail("command_levels curriculum names a reward term that does not exist");
+  return 0;
+}
+inline int TableBuild::observations() {
+  const rl_task_desc& t = d.task;
   if (t.n_policy > MAX_OBS || t.n_critic > MAX_OBS || t.n_rewards > MAX_T) return fail("too many terms");
   T.n_policy = t.n_policy; T.n_critic = t.n_critic; T.policy_corrupt = t.policy_corrupt; T.critic_corrupt = t.critic_corrupt;
   for (int grp = 0; grp < 2; ++grp) {
@@ -429,6 +467,10 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
     // the non-scan columns are stored densely: column of ordinal n is n (before the scan) or n + scan_n (after it)
   }
   T.scan_nx = t.scan_nx; T.scan_ny = t.scan_ny; T.scan_res = t.scan_res; T.scan_offset = t.scan_offset; T.wheel_joint_mask = t.wheel_joint_mask;
+  return 0;
+}
+inline int TableBuild::rewards() {
+  const rl_task_desc& t = d.task;
   T.n_rewards = t.n_rewards;
   int pool_used = 0;
   for (int i = 0; i < t.n_rewards; ++i) {
@@ -479,6 +521,10 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
     const int LPE16 = 16;
     T.n_main = t.n_rewards <= LPE16 ? t.n_rewards : std::max(LPE16, t.n_rewards - n_scalar);
   }
+  return 0;
+}
+inline int TableBuild::terminations() {
+  const rl_task_desc& t = d.task;
   T.term_time_out = t.term_time_out; T.term_oob = t.term_out_of_bounds; T.term_illegal = t.term_illegal_contact;
   if (const char* tv = std::getenv("RL_ENV_TERMS"))  // RL_ENV_TERMS=0: no termination term, so no env ever resets inside step() (timing A/Bs: what the reset path costs a launch)
     if (atoi(tv) == 0) {
@@ -501,6 +547,22 @@ inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_
   return 0;
 }
 
+inline int build_tables(const rl_env_desc& d, Tables& T, std::vector<int>& body_lane, std::vector<int>& body_slot, std::vector<int>& link_lane_out,
+                        std::vector<int>& link_pos_out, bool merge = false) {
+  memset(&T, 0, sizeof(T));
+  const rl_model_desc& m = d.model;
+  int CL, NW, SPL, NBS, rotpad;
+  if (topo_shape(m, CL, NW, SPL, NBS, rotpad)) return -1;
+  const int NGRP = CL + 1;
+  if (merge && !(NW == 0 && CL == 4 && !rotpad)) return fail("merged base share: 4-joint quadruped limbs (same length, unrotated joint frames) only");
+  T.CL = CL; T.NW = NW; T.SPL = SPL; T.NBS = NBS; T.nw_used = m.num_trunk; T.merged = merge ? 1 : 0; T.rotpad = rotpad;
+  TableBuild B{d, m, T, body_lane, body_slot, link_lane_out, link_pos_out, merge, CL, NW, SPL, NBS, NGRP};
+  if (B.topology() || B.self_collision() || B.body_slots() || B.sphere_slots() || B.sublane_slots() || B.addressed() || B.scalars() || B.observations() ||
+      B.rewards() || B.terminations())
+    return -1;
+  return 0;
+}
+
 // descriptor -> Tables as rl_env_create does it (tools/gen_specs.py compiles the specialised term stacks from the same call)
 inline int compile_tables(const rl_env_desc& d, Tables& tables, std::vector<int>& body_lane, std::vector<int>& body_slot, std::vector<int>& link_lane,
                           std::vector<int>& link_pos) {
@@ -519,23 +581,34 @@ inline int compile_tables(const rl_env_desc& d, Tables& tables, std::vector<int>
 }
 
 // packed (per-instance) table image that the env kernels stage into LDS
+// A merged task's image is built and read as TablesT<TopoQuad4M>; code that knows the chain length only may take it for TablesT<TopoQuad4>:
+// the two layouts are the same (M0 changes what the lane program does with the sphere slots, not where they are)
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"
+#define RL_SAME_OFFSET(S, M) static_assert(offsetof(S<TopoQuad4M>, M) == offsetof(S<TopoQuad4>, M), "merged instance: layout of " #S "::" #M)
+static_assert(sizeof(TablesT<TopoQuad4M>) == sizeof(TablesT<TopoQuad4>) && sizeof(LaneTabT<TopoQuad4M>) == sizeof(LaneTabT<TopoQuad4>), "merged instance: table size");
+RL_SAME_OFFSET(TablesT, lane); RL_SAME_OFFSET(TablesT, obs); RL_SAME_OFFSET(TablesT, rew);
+RL_SAME_OFFSET(LaneTabT, jc); RL_SAME_OFFSET(LaneTabT, rota); RL_SAME_OFFSET(LaneTabT, sph); RL_SAME_OFFSET(LaneTabT, rot0); RL_SAME_OFFSET(LaneTabT, vel_limit);
+RL_SAME_OFFSET(LaneTabT, q0); RL_SAME_OFFSET(LaneTabT, qd0); RL_SAME_OFFSET(LaneTabT, soft_lo); RL_SAME_OFFSET(LaneTabT, soft_hi); RL_SAME_OFFSET(LaneTabT, kp0);
+RL_SAME_OFFSET(LaneTabT, kd0); RL_SAME_OFFSET(LaneTabT, action_is_vel); RL_SAME_OFFSET(LaneTabT, a_scale); RL_SAME_OFFSET(LaneTabT, a_off); RL_SAME_OFFSET(LaneTabT, a_lo);
+RL_SAME_OFFSET(LaneTabT, a_hi); RL_SAME_OFFSET(LaneTabT, joint_id); RL_SAME_OFFSET(LaneTabT, joint_own); RL_SAME_OFFSET(LaneTabT, nj); RL_SAME_OFFSET(LaneTabT, attach);
+RL_SAME_OFFSET(LaneTabT, grp0_depth); RL_SAME_OFFSET(LaneTabT, sph_slot); RL_SAME_OFFSET(LaneTabT, slot_body); RL_SAME_OFFSET(LaneTabT, slot_grp); RL_SAME_OFFSET(LaneTabT, slot_pos);
+RL_SAME_OFFSET(LaneTabT, base_body_local); RL_SAME_OFFSET(LaneTabT, owns_base_body); RL_SAME_OFFSET(LaneTabT, sph_base_mask); RL_SAME_OFFSET(LaneTabT, own_slot); RL_SAME_OFFSET(LaneTabT, own_slot2);
+#undef RL_SAME_OFFSET
+#pragma GCC diagnostic pop
 inline size_t packed_size(const TaskTab& T) {
-  return T.NW > 3 ? sizeof(TablesT<TopoGR>) : T.NW > 0 ? sizeof(TablesT<TopoG1>) : (T.rotpad ? sizeof(TablesT<TopoQuad4R>) : T.CL == 4 ? sizeof(TablesT<TopoQuad4>) : sizeof(TablesT<TopoQuad3>));
+  size_t n = 0;
+  visit_instance(T, [&](auto tp) { n = sizeof(TablesT<typename decltype(tp)::type>); });
+  return n;
 }
-template <class TP>
-inline size_t staged_bytes_t(const TaskTab& T) {  // `rew` is the last member: everything up to its first n_rewards entries
-  return (sizeof(TablesBody<TP>) - (size_t)(MAX_T - T.n_rewards) * sizeof(RewTab) + 15) / 16 * 16;
-}
-inline size_t staged_bytes(const TaskTab& T) {
-  return T.NW > 3 ? staged_bytes_t<TopoGR>(T) : T.NW > 0 ? staged_bytes_t<TopoG1>(T) : (T.rotpad ? staged_bytes_t<TopoQuad4R>(T) : T.CL == 4 ? staged_bytes_t<TopoQuad4>(T) : staged_bytes_t<TopoQuad3>(T));
+inline size_t staged_bytes(const TaskTab& T) {  // `rew` is the last member: everything up to its first n_rewards entries
+  size_t n = 0;
+  visit_instance(T, [&](auto tp) { n = (sizeof(TablesBody<typename decltype(tp)::type>) - (size_t)(MAX_T - T.n_rewards) * sizeof(RewTab) + 15) / 16 * 16; });
+  return n;
 }
 inline std::vector<uint8_t> pack_image(const Tables& T) {
   std::vector<uint8_t> img(packed_size(T), 0);
-  if (T.NW > 3) pack_tables<TopoGR>(T, *reinterpret_cast<TablesT<TopoGR>*>(img.data()));
-  else if (T.NW > 0) pack_tables<TopoG1>(T, *reinterpret_cast<TablesT<TopoG1>*>(img.data()));
-  else if (T.rotpad) pack_tables<TopoQuad4R>(T, *reinterpret_cast<TablesT<TopoQuad4R>*>(img.data()));
-  else if (T.CL == 4) pack_tables<TopoQuad4>(T, *reinterpret_cast<TablesT<TopoQuad4>*>(img.data()));
-  else pack_tables<TopoQuad3>(T, *reinterpret_cast<TablesT<TopoQuad3>*>(img.data()));
+  visit_instance(T, [&](auto tp) { pack_tables(T, *reinterpret_cast<TablesT<typename decltype(tp)::type>*>(img.data())); });
   return img;
 }
 
@@ -552,7 +625,7 @@ struct EnvImpl {
   KState S;
   CmdLevelParams cmd_level_params{};
   int spec_id = 0;  // env_spec.h: the specialised step kernel this env runs (0: the interpreter)
-  int N = 0, Npad = 0, D = 0, B = 0, CL = 0, inst = 0, ept = ENVS_PER_WAVE;  // inst: lane-program instance key (CL, + 100 merged, + 200 six-joint trunk, + 400 rot / pad quadruped)
+  int N = 0, Npad = 0, D = 0, B = 0, CL = 0, inst = 0, ept = ENVS_PER_WAVE;  // inst: lane-program instance key (env_tables.h instance_key)
   uint64_t seed = 0;
   uint32_t step_counter = 0;
   // the kernels take the step count as *step_base + launch literal (rl_env_graph_*): `anchor` mirrors the device word
@@ -607,7 +680,7 @@ struct EnvImpl {
     }
     be.spec_id = spec_id;
     CL = tables.CL;
-    inst = tables.CL + (tables.merged ? 100 : 0) + (tables.NW > 3 ? 200 : 0) + (tables.rotpad ? 400 : 0);
+    inst = instance_key(tables);
     if (be.init(device)) return fail("device init failed: " + be.error());
     ept = be.envs_per_wave(tables, Npad);  // the lane mapping (16 or 4 lanes per env) decides the layout of the state tiles
     if (std::getenv("RL_ENV_DEBUG")) fprintf(stderr, "rl_env: lane program CL %d NW %d merged %d rot/pad %d, %d envs per wavefront\n", tables.CL, tables.NW, tables.merged, tables.rotpad, ept);

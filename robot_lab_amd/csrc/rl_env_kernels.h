@@ -411,18 +411,37 @@ hipError_t launch_w(const LaunchCfg& cfg, const KState& S, const void* T, size_t
   }
   return hipGetLastError();
 }
+// THE rule for four-wavefront workgroups (launch_cl below, and the plan rl_env_plan reports): the launch has a wavefront for every SIMD
+// and four wavefront regions behind ONE table image fit a CU's LDS.  (The trunk + limbs instance with 16 lanes per env gains nothing:
+// 174.4 vs 173.8 us with two wavefronts per workgroup - and its 80 KB per wavefront leave no room; with 32 lanes per env four ~32 KB
+// wavefronts and one table image are what lets a CU hold four.)
+inline bool four_wave_workgroup(const LaunchCfg& cfg, int NW, int sub, int tiles, size_t lds1, size_t table_bytes) {
+  return (NW == 0 || sub == 8) && cfg.wg_waves == 4 && (tiles >= 4 * cfg.n_cu || cfg.wg_force) && table_bytes + 4 * (lds1 - table_bytes) <= 160 * 1024;
+}
 template <class TP, int SUB, class SP = NoSpec>
 hipError_t launch_cl(const LaunchCfg& cfg, const KState& S, const void* T, size_t lds1, hipStream_t st) {
-  // (the trunk + limbs instance with 16 lanes per env gains nothing: 174.4 vs 173.8 us with two wavefronts per workgroup - and its 80 KB
-  // per wavefront leave no room; with 32 lanes per env four ~32 KB wavefronts and ONE table image are what lets a CU hold four)
-  if constexpr (TP::NW == 0 || SUB == 8) {
-    const int tiles = S.Npad / (16 / SUB);
-    const size_t lds4 = S.table_bytes + 4 * (lds1 - S.table_bytes);
+  if constexpr (TP::NW == 0 || SUB == 8) {  // (the other mappings have no four-wavefront kernel)
     // (only the step kernel exists in the four-wavefront shape: resets and the halves of a split step are off the hot path)
-    if (cfg.wg_waves == 4 && (tiles >= 4 * cfg.n_cu || cfg.wg_force) && lds4 <= 160 * 1024 && S.mode == KMODE_STEP)
+    if (four_wave_workgroup(cfg, TP::NW, SUB, S.Npad / (16 / SUB), lds1, S.table_bytes) && S.mode == KMODE_STEP)
       return launch_w<TP, SUB, 4, SP>(cfg, S, T, lds1, st);
   }
   return launch_w<TP, SUB, 1, SP>(cfg, S, T, lds1, st);
+}
+
+// Launch of the interpreter's kernels of the instance with key `inst` in lane mapping SUB; a hipError_t, or -2 when the build does not carry
+// them.  -DRL_ENV_ONLY=<key * 10 + SUB> (e.g. 34; 1044: merged): build that one instance only - kernel experiments compile in 15 s instead
+// of 80.  (The filter sits in a generic lambda: a filtered-out launch_cl is not instantiated.)
+#ifndef RL_ENV_ONLY
+#define RL_ENV_ONLY 0
+#endif
+template <int SUB>
+int launch_inst(const LaunchCfg& cfg, const KState& S, const void* T, int inst, size_t lds1, hipStream_t st) {
+  int rc = -2;
+  visit_instance(inst, [&](auto tp) {
+    using TP = typename decltype(tp)::type;
+    if constexpr (instance_has_sub<TP, SUB>() && (RL_ENV_ONLY == 0 || RL_ENV_ONLY == instance_key<TP>() * 10 + SUB)) rc = (int)launch_cl<TP, SUB>(cfg, S, T, lds1, st);
+  });
+  return rc;
 }
 
 // Launch of the step kernel SPECIALISED on the task of Spec SP (env_spec.h) in lane mapping `sub`; a hipError_t, or -2 when there is no

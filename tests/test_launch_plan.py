@@ -49,3 +49,25 @@ def test_forced_mappings_are_reported(monkeypatch):
         monkeypatch.setenv("RL_ENV_WG", "-4")
         p = capi.plan(desc, 512, 256)
         assert p["lanes_per_limb"] == sub and p["wavefronts_per_workgroup"] == 4 and p["lds_bytes_per_workgroup"] <= LDS_PER_CU
+
+
+# what a forced RL_ENV_SUB falls back to when the task's lane-program instance has no such mapping: (task, RL_ENV_SUB, lanes per limb reported)
+FORCED = [("RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0", 8, 4)]  # quadrupeds have no eight-lane mapping: 4
+for _task in ("RobotLab-Isaac-Velocity-Rough-Unitree-G1-v0", "RobotLab-Isaac-Velocity-Rough-FFTAI-GR1T1-v0"):
+    FORCED += [(_task, 2, 4), (_task, 8, 8), (_task, 1, None)]  # trunk + limbs: no lane-pair mapping: 4; one lane per limb: refused
+for _task in ("RobotLab-Isaac-Velocity-Rough-Unitree-Go2W-v0", "RobotLab-Isaac-Velocity-Rough-DDTRobot-Tita-v0"):  # merged / rot-pad instance
+    FORCED += [(_task, 4, 4), (_task, 2, 2), (_task, 1, 1)]
+
+
+@pytest.mark.parametrize("task,sub,lanes", FORCED, ids=[f"{t.split('-')[-2]}-sub{s}" for t, s, _ in FORCED])
+def test_forced_mapping_fallbacks(task, sub, lanes, monkeypatch):
+    for k in ("RL_ENV_WG", "RL_ENV_MERGE", "RL_ENV_COST8"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("RL_ENV_SUB", str(sub))
+    desc, extra = load_bundle(task)
+    build_world(desc, extra, 16, 0)
+    if lanes is None:
+        with pytest.raises(capi.RlEnvError, match="needs more LDS than a CU has"):
+            capi.plan(desc, 512, 256)
+    else:
+        assert capi.plan(desc, 512, 256)["lanes_per_limb"] == lanes
