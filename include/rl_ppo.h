@@ -12,6 +12,10 @@
  * (no floating-point atomics): the same state and permutation give bit-identical parameters.
  * Symmetry: rl_ppo_set_symmetry (data augmentation) and, on its tables, rl_ppo_set_mirror_loss (rsl_rl's mirror loss, with or without
  * the augmentation); a handle on which neither was called launches the kernels of a learner without them.
+ * Several GPUs (rsl_rl's multi-GPU contract, robot_lab_amd/dist.py): rl_ppo_set_world, then per update rl_ppo_update_begin and per mini-batch
+ * rl_ppo_minibatch_local -> the CALLER's SUM all-reduce of the wire (rl_ppo_wire: the flat gradient and the KL statistic in one buffer, so
+ * one collective per mini-batch) -> rl_ppo_minibatch_apply.  The library holds no communicator; the split sequence only enqueues as well.
+ * Optimiser state for checkpoints: rl_ppo_get_flat / rl_ppo_set_flat (the moments), rl_ppo_get_optimizer / rl_ppo_set_optimizer.
  *
  * All `*_dev` pointers are DEVICE pointers.  Flat layout (parameters, gradients, Adam moments), the order of
  * `ActorCritic.parameters()`: std[act], then per actor layer W[out][in], b[out], then the critic's layers alike. */
@@ -107,6 +111,34 @@ int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* i
 /* The whole PPO.update: num_learning_epochs x num_mini_batches mini-batches of n_rows / num_mini_batches rows, mini-batch i of every epoch
  * taking perm_dev[i * mb .. (i + 1) * mb).  Enqueues only. */
 int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev, int32_t n_rows, void* stream);
+
+/* ---- the update of one rank among `world_size`: the mini-batch split around the caller's collective ----
+ * rl_ppo_set_world: how many ranks SUM their wires.  Called once, before the first mini-batch; no device work.  Refused with a reason:
+ * world_size < 1, a second call, a call after the first mini-batch.  Never called, or called with 1: the kernels and the results of a
+ * learner on its own. */
+int rl_ppo_set_world(rl_ppo* p, int32_t world_size);
+/* The wire: *dev = the flat gradient buffer, *count = rl_ppo_num_parameters + 1.  Words [0, P) are the gradient, word [P] is this rank's
+ * KL statistic of the last rl_ppo_minibatch_local (fp32, the mean over its stored rows; 0 with the fixed schedule).  The buffer is padded
+ * past `count` to a multiple of 64 floats.  The address is fixed for the life of the handle. */
+int rl_ppo_wire(rl_ppo* p, float** dev, int64_t* count);
+/* the stream-ordered zeroing of the statistics of an update (what rl_ppo_update does at its head) */
+int rl_ppo_update_begin(rl_ppo* p, void* stream);
+/* rl_ppo_minibatch_grad + the rank-local statistics of the mini-batch (value loss, surrogate, entropy, L_mirror) + the KL word of the wire.
+ * Moves neither the learning rate nor the step counter.  Every call is followed by one rl_ppo_minibatch_apply (refused otherwise). */
+int rl_ppo_minibatch_local(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream);
+/* After the caller has SUM-all-reduced the wire over the world (in stream order): kl = word[P] / (float)world moves the learning rate as
+ * rl_ppo_update's mini-batch does (same expressions), the KL sum, the step and the mini-batch count are booked, then sum of squares ->
+ * clip -> Adam -> floor of std run on g[i] / (float)world - a division in fp32, the torch learner's `flat /= world_size` element for
+ * element.  With a world of 1 nothing is divided: begin + n x (local, apply) is rl_ppo_update bit for bit. */
+int rl_ppo_minibatch_apply(rl_ppo* p, void* stream);
+
+/* ---- optimiser state (checkpoints) ----
+ * which: 2 Adam first moment, 3 Adam second moment <- src_dev[rl_ppo_num_parameters]; stream-ordered device-to-device copy. */
+int rl_ppo_set_flat(rl_ppo* p, int32_t which, const float* src_dev, void* stream);
+/* the learning-rate word and the Adam step counter.  get: waits for `stream`, one small copy.  set: stream-ordered; refused: a learning
+ * rate that is not finite and > 0, a negative step. */
+int rl_ppo_get_optimizer(rl_ppo* p, double* lr, int64_t* step, void* stream);
+int rl_ppo_set_optimizer(rl_ppo* p, double lr, int64_t step, void* stream);
 
 /* out[8]: mean value loss, mean surrogate loss, mean entropy, mean KL (0 unless adaptive), learning rate, last pre-clip gradient norm,
  * mini-batches in the last update, Adam step counter.  Waits for `stream`, one small copy. */

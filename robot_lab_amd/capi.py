@@ -213,7 +213,8 @@ class NativeEnv:
 PPO_LIB = os.path.join(_HERE, "csrc", "librl_ppo_hip.so")
 PPO_EXPORTS = ["rl_ppo_create", "rl_ppo_destroy", "rl_ppo_last_error", "rl_ppo_num_parameters", "rl_ppo_set_parameters", "rl_ppo_get_parameters",
                "rl_ppo_parameter_pointers", "rl_ppo_get_flat", "rl_ppo_minibatch_grad", "rl_ppo_update", "rl_ppo_stats", "rl_ppo_set_symmetry",
-               "rl_ppo_set_mirror_loss", "rl_ppo_stats_ex"]
+               "rl_ppo_set_mirror_loss", "rl_ppo_stats_ex", "rl_ppo_set_world", "rl_ppo_wire", "rl_ppo_update_begin", "rl_ppo_minibatch_local",
+               "rl_ppo_minibatch_apply", "rl_ppo_set_flat", "rl_ppo_get_optimizer", "rl_ppo_set_optimizer"]
 _ppo_lib = None
 
 
@@ -258,6 +259,14 @@ def load_ppo_library(path: str | None = None) -> C.CDLL:
     lib.rl_ppo_set_symmetry.argtypes = [C.c_void_p, C.c_int32, ip, fp, ip, fp, ip, fp]
     lib.rl_ppo_set_mirror_loss.argtypes = [C.c_void_p, C.c_float, C.c_int32]
     lib.rl_ppo_stats_ex.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p]
+    lib.rl_ppo_set_world.argtypes = [C.c_void_p, C.c_int32]
+    lib.rl_ppo_wire.argtypes = [C.c_void_p, pp, C.POINTER(C.c_int64)]
+    lib.rl_ppo_update_begin.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rl_ppo_minibatch_local.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.rl_ppo_minibatch_apply.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rl_ppo_set_flat.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.rl_ppo_get_optimizer.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p]
+    lib.rl_ppo_set_optimizer.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_void_p]
     if path == PPO_LIB:
         _ppo_lib = lib
     return lib

@@ -19,6 +19,10 @@
 //             stored rows, and a row of a copy >= 1 carries the mirror gradient alone
 //   step      sum of squares in fixed blocks -> every block of the Adam kernel adds the same partials in the same order: norm, clip
 //             coefficient, Adam, floor of std
+//   world     (rl_ppo_set_world) one rank among several: rl_ppo_minibatch_local ends after the reduce launch and leaves the flat gradient and,
+//             in word [P] behind it, the rank's KL statistic (the LOCAL side of the head-finish kernel) in the WIRE; the caller SUM-all-reduces
+//             it; rl_ppo_minibatch_apply moves the learning rate from word [P] / world in a one-workgroup kernel and runs `step` on
+//             g[i] / world (the SCALED sides of its two kernels; fp32 divisions, as the torch learner's `flat /= world_size`)
 // The three GEMM shapes are one LDS-tiled kernel (128 x 128 output tile, 16-deep slices, four wavefronts of 64 x 64 = 2 x 2
 // v_mfma_f32_32x32x2_f32 tiles: exact fp32 products, fp32 accumulation in contraction order).
 #include <hip/hip_runtime.h>
@@ -369,10 +373,14 @@ __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
   }
 }
 
-// one workgroup of 64: orders the head's partial sums; with `apply` it books the statistics, moves the learning rate and counts the step
+// one workgroup of 64: orders the head's partial sums; with `apply` it books the statistics, moves the learning rate and counts the step.
+// LOCAL (rl_ppo_minibatch_local, always with `apply`): it books the rank-local statistics and leaves the KL statistic in `kl_word` - the
+// learning rate, the KL sum and the counters are ppo_world_apply_kernel's, after the caller's all-reduce.  LOCAL = false never reads `kl_word`
 // (n: rows of the loss means; n_kl: rows of the KL mean - the stored rows under symmetry augmentation)
+enum { APPLY_NONE = 0, APPLY_FUSED = 1, APPLY_LOCAL = 2 };
+template <bool LOCAL>
 __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* partials, int nblocks, int n, int n_kl, const float* std, int A, DevState* st,
-                                                            int apply, int adaptive, double desired_kl) {
+                                                            int apply, int adaptive, double desired_kl, float* kl_word) {
   __shared__ double sh[3][64];
   for (int q = 0; q < 3; ++q) {
     double s = 0.0;
@@ -392,6 +400,10 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* parti
   st->acc[0] += (double)(float)(sh[1][0] / (double)n);
   st->acc[1] += (double)(float)(sh[0][0] / (double)n);
   st->acc[2] += (double)ent;
+  if (LOCAL) {
+    *kl_word = adaptive ? kl : 0.f;
+    return;
+  }
   if (adaptive) {  // (rl_ppo_create: adaptive implies desired_kl > 0)
     // the host learner compares an fp32 statistic with thresholds formed in fp64
     if (kl > (float)(2.0 * desired_kl)) st->lr = fmax(1e-5, st->lr / 1.5);
@@ -416,13 +428,37 @@ __global__ __launch_bounds__(64) void ppo_mirror_finish_kernel(const double* par
   if (threadIdx.x == 0 && apply) st->mirror_acc += (double)(float)(sh[0] / count);
 }
 
-// ---- optimiser step
+// what ppo_head_finish_kernel does under APPLY_FUSED past the local statistics, on the all-reduced wire word: the KL statistic is the ranks'
+// SUM / world in fp32 (dist.py `LearnerGroup.mean`), the learning-rate decision uses the same expressions
+__global__ __launch_bounds__(64) void ppo_world_apply_kernel(const float* kl_word, float world, DevState* st, int adaptive, double desired_kl) {
+  if (threadIdx.x != 0) return;
+  if (adaptive) {
+    const float kl = *kl_word / world;
+    if (kl > (float)(2.0 * desired_kl)) st->lr = fmax(1e-5, st->lr / 1.5);
+    else if (kl > 0.f && kl < (float)(desired_kl / 2.0)) st->lr = fmin(1e-2, st->lr * 1.5);
+    st->acc[3] += (double)kl;
+  }
+  st->step += 1;
+  st->n_minibatches += 1;
+}
+
+__global__ void ppo_set_optimizer_kernel(DevState* st, double lr, long long step) {
+  st->lr = lr;
+  st->step = step;
+}
+
+// ---- optimiser step.  SCALED (rl_ppo_minibatch_apply with a world > 1): g holds the ranks' SUM and every entry is read as g[i] / world, a
+// division in fp32 as `flat /= world_size` of the torch learner; SCALED = false never reads `world`
 constexpr int NORM_BLOCKS = 256;
-__global__ __launch_bounds__(256) void ppo_sumsq_kernel(const float* g, long n, double* partial) {
+template <bool SCALED>
+__global__ __launch_bounds__(256) void ppo_sumsq_kernel(const float* g, long n, double* partial, float world) {
   __shared__ double sh[256];
   const long per = (n + NORM_BLOCKS - 1) / NORM_BLOCKS, b0 = (long)blockIdx.x * per, b1 = b0 + per < n ? b0 + per : n;
   double s = 0.0;
-  for (long i = b0 + threadIdx.x; i < b1; i += 256) s += (double)g[i] * (double)g[i];
+  for (long i = b0 + threadIdx.x; i < b1; i += 256) {
+    const float gi = SCALED ? g[i] / world : g[i];
+    s += (double)gi * (double)gi;
+  }
   sh[threadIdx.x] = s;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -433,8 +469,9 @@ __global__ __launch_bounds__(256) void ppo_sumsq_kernel(const float* g, long n, 
 }
 
 // clip_grad_norm_ (coef = min(1, max_norm / (norm + 1e-6))) + torch.optim.Adam's step (defaults) + the floor of std (the first n_std entries)
+template <bool SCALED>
 __global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g, float* m1, float* m2, long n, int n_std, const double* partial, DevState* st,
-                                                      float max_norm) {
+                                                      float max_norm, float world) {
   __shared__ double sh[256];
   sh[threadIdx.x] = partial[threadIdx.x];  // NORM_BLOCKS == blockDim.x; every block adds the same numbers in the same order
   __syncthreads();
@@ -450,7 +487,7 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g,
   const double step = (double)st->step;
   const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
   const float step_size = (float)(st->lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  const float gi = g[i] * coef;
+  const float gi = (SCALED ? g[i] / world : g[i]) * coef;
   const float m = m1[i] + 0.1f * (gi - m1[i]);                       // exp_avg.lerp_(grad, 1 - beta1)
   const float v = m2[i] * 0.999f + (float)(1.0 - 0.999) * gi * gi;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
   m1[i] = m;
@@ -500,6 +537,8 @@ struct rl_ppo {
   float mirror = 0.f;             // coefficient of the mirror loss; 0: rl_ppo_set_mirror_loss was not called
   bool augment = true;            // (mirror loss) the PPO terms see every copy; false: the stored rows only
   double* mirror_part = nullptr;  // the head's fourth partials
+  int world = 0;                  // ranks whose gradients the caller sums into the wire; 0: rl_ppo_set_world was not called (one rank)
+  bool local_pending = false;     // rl_ppo_minibatch_local ran and rl_ppo_minibatch_apply has not yet
 };
 
 namespace {
@@ -545,6 +584,9 @@ bool alloc_rows(rl_ppo* p, size_t rows) {
   return p->rows_ready;
 }
 
+// the flat gradient buffer is the WIRE of a multi-rank update: P gradient words, the KL word [P], padded to a multiple of 64 floats
+size_t wire_floats(long n_params) { return ((size_t)n_params + 1 + 63) / 64 * 64; }
+
 int check_launch() {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
@@ -555,8 +597,24 @@ int chunk_rows(int n, int S) {  // rows per chunk: a multiple of the GEMM's slic
   return std::max(TK, (c + TK - 1) / TK * TK);
 }
 
-// the launches of one mini-batch (see the head of this file)
-int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool apply, hipStream_t s) {
+// sum of squares -> clip -> Adam -> floor of std on the flat gradient; with a world > 1 on g[i] / world (the wire holds the ranks' SUM)
+void optimiser_step(rl_ppo* p, hipStream_t s) {
+  const float world = (float)std::max(p->world, 1);
+  const dim3 adam_grid((unsigned)((p->n_params + 255) / 256));
+  if (p->world > 1) {
+    hipLaunchKernelGGL(ppo_sumsq_kernel<true>, dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part, world);
+    hipLaunchKernelGGL(ppo_adam_kernel<true>, adam_grid, dim3(256), 0, s, p->params, p->grads, p->m1, p->m2, p->n_params, p->A, p->norm_part, p->st,
+                       p->hp.max_grad_norm, world);
+  } else {
+    hipLaunchKernelGGL(ppo_sumsq_kernel<false>, dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part, world);
+    hipLaunchKernelGGL(ppo_adam_kernel<false>, adam_grid, dim3(256), 0, s, p->params, p->grads, p->m1, p->m2, p->n_params, p->A, p->norm_part, p->st,
+                       p->hp.max_grad_norm, world);
+  }
+}
+
+// the launches of one mini-batch (see the head of this file); `apply`: APPLY_NONE (the gradient alone), APPLY_FUSED (statistics, learning rate
+// and the optimiser step follow on the device), APPLY_LOCAL (the rank-local statistics and the KL word of the wire; no optimiser step)
+int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int apply, hipStream_t s) {
   const int L = p->L;
   const bool sym = p->n_sym > 0;
   const int n = sym ? p->n_sym * n0 : n0;  // the rows every stage past the layer-0 fetch sees
@@ -598,8 +656,13 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
     if (mirror) hipLaunchKernelGGL((ppo_head_kernel<true, true>), dim3(blocks), dim3(256), 0, s, a);
     else if (sym) hipLaunchKernelGGL(ppo_head_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(ppo_head_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0, p->params, p->A, p->st, apply ? 1 : 0,
-                       p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0, p->hp.desired_kl);
+    const int adaptive = p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0;
+    if (apply == APPLY_LOCAL)
+      hipLaunchKernelGGL(ppo_head_finish_kernel<true>, dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0, p->params, p->A, p->st, 1, adaptive,
+                         p->hp.desired_kl, p->grads + p->n_params);
+    else
+      hipLaunchKernelGGL(ppo_head_finish_kernel<false>, dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0, p->params, p->A, p->st, apply ? 1 : 0,
+                         adaptive, p->hp.desired_kl, (float*)nullptr);
     if (mirror)
       hipLaunchKernelGGL(ppo_mirror_finish_kernel, dim3(1), dim3(64), 0, s, p->mirror_part, blocks, (double)(p->n_sym - 1) * (double)n0 * (double)p->A, p->st,
                          apply ? 1 : 0);
@@ -654,11 +717,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, bool
     hipLaunchKernelGGL(ppo_colsum_kernel, dim3(colx, Smax, np + 1), dim3(256), 0, s, cb);
     hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)std::min<long>((redmax + 255) / 256, 512), np + 1), dim3(256), 0, s, rb);
   }
-  if (apply) {
-    hipLaunchKernelGGL(ppo_sumsq_kernel, dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part);
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, s, p->params, p->grads, p->m1, p->m2, p->n_params, p->A,
-                       p->norm_part, p->st, p->hp.max_grad_norm);
-  }
+  if (apply == APPLY_FUSED) optimiser_step(p, s);
   return check_launch();
 }
 
@@ -689,6 +748,14 @@ int copy_parameters(rl_ppo* p, const float* const* aw, const float* const* ab, c
       if (B[k] && cp(B[k][l], N.b_off[l], (size_t)N.dims[l + 1])) return -1;
     }
   if (sd && cp(sd, 0, (size_t)p->A)) return -1;
+  return 0;
+}
+
+// the statistics of an update start at zero (stream-ordered: the previous update's are read by rl_ppo_stats before)
+int reset_statistics(rl_ppo* p, hipStream_t s) {
+  if (hipMemsetAsync(p->st->acc, 0, sizeof(double) * 4, s) != hipSuccess || hipMemsetAsync(&p->st->n_minibatches, 0, sizeof(long long), s) != hipSuccess)
+    return fail("cannot reset the statistics block");
+  if (p->mirror > 0.f && hipMemsetAsync(&p->st->mirror_acc, 0, sizeof(double), s) != hipSuccess) return fail("cannot reset the statistics block");
   return 0;
 }
 
@@ -737,7 +804,7 @@ int rl_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t
     }
   }
   p->n_params = off;
-  bool ok = dalloc(p, &p->params, (size_t)off) && dalloc(p, &p->grads, (size_t)off) && dalloc(p, &p->m1, (size_t)off) && dalloc(p, &p->m2, (size_t)off);
+  bool ok = dalloc(p, &p->params, (size_t)off) && dalloc(p, &p->grads, wire_floats(off)) && dalloc(p, &p->m1, (size_t)off) && dalloc(p, &p->m2, (size_t)off);
   ok = ok && dalloc(p, &p->norm_part, (size_t)NORM_BLOCKS) && dalloc(p, &p->st, 1);
   if (ok) {
     std::vector<float> ones((size_t)p->A, 1.0f);
@@ -858,7 +925,7 @@ int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* i
   if (check_batch(batch)) return -1;
   if (n_idx < 1 || n_idx > p->max_rows) return fail("n_idx outside 1..max_rows_per_minibatch");
   if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
-  return minibatch(p, batch, idx_dev, n_idx, false, (hipStream_t)stream);
+  return minibatch(p, batch, idx_dev, n_idx, APPLY_NONE, (hipStream_t)stream);
 }
 
 int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev, int32_t n_rows, void* stream) {
@@ -868,14 +935,86 @@ int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev,
   if (mb < 1 || mb > p->max_rows) return fail("rows per mini-batch outside 1..max_rows_per_minibatch");
   if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
-  // the statistics of THIS update start at zero (stream-ordered: the previous update's are read by rl_ppo_stats before)
-  if (hipMemsetAsync(p->st->acc, 0, sizeof(double) * 4, s) != hipSuccess || hipMemsetAsync(&p->st->n_minibatches, 0, sizeof(long long), s) != hipSuccess)
-    return fail("cannot reset the statistics block");
-  if (p->mirror > 0.f && hipMemsetAsync(&p->st->mirror_acc, 0, sizeof(double), s) != hipSuccess) return fail("cannot reset the statistics block");
+  if (p->local_pending) return fail("rl_ppo_update: an rl_ppo_minibatch_local waits for its rl_ppo_minibatch_apply");
+  if (reset_statistics(p, s)) return -1;
   for (int e = 0; e < p->hp.num_learning_epochs; ++e)
     for (int i = 0; i < p->hp.num_mini_batches; ++i)
-      if (minibatch(p, batch, perm_dev + (size_t)i * mb, mb, true, s)) return -1;
+      if (minibatch(p, batch, perm_dev + (size_t)i * mb, mb, APPLY_FUSED, s)) return -1;
   return 0;
+}
+
+int rl_ppo_set_world(rl_ppo* p, int32_t world_size) {
+  if (!p) return fail("null argument");
+  if (world_size < 1) return fail("rl_ppo_set_world: world_size " + std::to_string(world_size) + " must be >= 1");
+  if (p->world) return fail("rl_ppo_set_world: the world of this learner is already set (it is set once, before the first mini-batch)");
+  if (p->started) return fail("rl_ppo_set_world: refused after the first mini-batch - the replicas of a world start together; create a new learner");
+  p->world = world_size;  // (no device work: the wire is the gradient buffer, the divisor a kernel argument)
+  return 0;
+}
+
+int rl_ppo_wire(rl_ppo* p, float** dev, int64_t* count) {
+  if (!p || !dev || !count) return fail("null argument");
+  *dev = p->grads;
+  *count = p->n_params + 1;
+  return 0;
+}
+
+int rl_ppo_update_begin(rl_ppo* p, void* stream) {
+  if (!p) return fail("null argument");
+  if (p->local_pending) return fail("rl_ppo_update_begin: an rl_ppo_minibatch_local waits for its rl_ppo_minibatch_apply");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  return reset_statistics(p, (hipStream_t)stream);
+}
+
+int rl_ppo_minibatch_local(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream) {
+  if (!p || !idx_dev) return fail("null argument");
+  if (check_batch(batch)) return -1;
+  if (n_idx < 1 || n_idx > p->max_rows) return fail("n_idx outside 1..max_rows_per_minibatch");
+  if (p->local_pending) return fail("rl_ppo_minibatch_local: the previous mini-batch waits for its rl_ppo_minibatch_apply");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (minibatch(p, batch, idx_dev, n_idx, APPLY_LOCAL, (hipStream_t)stream)) return -1;
+  p->local_pending = true;
+  return 0;
+}
+
+int rl_ppo_minibatch_apply(rl_ppo* p, void* stream) {
+  if (!p) return fail("null argument");
+  if (!p->local_pending) return fail("rl_ppo_minibatch_apply: no rl_ppo_minibatch_local precedes it (the wire holds no gradient of this mini-batch)");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ppo_world_apply_kernel, dim3(1), dim3(64), 0, s, p->grads + p->n_params, (float)std::max(p->world, 1), p->st,
+                     p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0, p->hp.desired_kl);
+  optimiser_step(p, s);
+  p->local_pending = false;
+  return check_launch();
+}
+
+int rl_ppo_set_flat(rl_ppo* p, int32_t which, const float* src_dev, void* stream) {
+  if (!p || !src_dev) return fail("null argument");
+  if (which != 2 && which != 3) return fail("rl_ppo_set_flat: which must be 2 or 3 (the Adam moments; parameters go through rl_ppo_set_parameters)");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  const hipError_t e = hipMemcpyAsync(which == 2 ? p->m1 : p->m2, src_dev, (size_t)p->n_params * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
+}
+
+int rl_ppo_get_optimizer(rl_ppo* p, double* lr, int64_t* step, void* stream) {
+  if (!p || !lr || !step) return fail("null argument");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("stream synchronisation failed");
+  DevState st{};
+  if (hipMemcpy(&st, p->st, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return fail("optimiser state copy failed");
+  *lr = st.lr;
+  *step = (int64_t)st.step;
+  return 0;
+}
+
+int rl_ppo_set_optimizer(rl_ppo* p, double lr, int64_t step, void* stream) {
+  if (!p) return fail("null argument");
+  if (!std::isfinite(lr) || !(lr > 0.0)) return fail("rl_ppo_set_optimizer: the learning rate must be finite and > 0");
+  if (step < 0) return fail("rl_ppo_set_optimizer: the step counter must be >= 0");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  hipLaunchKernelGGL(ppo_set_optimizer_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, p->st, lr, (long long)step);
+  return check_launch();
 }
 
 namespace {

@@ -96,6 +96,16 @@ class LearnerGroup:
             g.copy_(flat[off:off + g.numel()].view_as(g))
             off += g.numel()
 
+    def all_reduce_sum(self, tensor: torch.Tensor) -> torch.Tensor:
+        """In-place SUM over the ranks, nothing else: the collective of the HIP learner (`ppo_hip.HipPPO(group=...)`), whose wire carries the
+        flat gradient and the KL statistic together and whose kernels divide by the world themselves.  RCCL: enqueued on the current stream,
+        no host wait.  gloo (RL_SHARE_GPU=1, the self-test): through the host, as `reduce_gradients`."""
+        if self.enabled:
+            import torch.distributed as dist
+
+            dist.all_reduce(tensor, op=dist.ReduceOp.SUM)
+        return tensor
+
     def mean(self, value: torch.Tensor) -> torch.Tensor:
         """a scalar statistic (the KL of the adaptive schedule) averaged over the ranks: the same number everywhere, hence the same
         learning-rate decision on every rank"""

@@ -217,8 +217,8 @@ def mirror_repr(alg):
 
 class Trainer:
     """collect (HIP, one graph launch) -> update -> push parameters, repeated: `OnPolicyRunner.learn` in miniature.
-    `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (single GPU),
-    pushed into the inference kernels device to device; `state_dict()` is rsl_rl's layout with either.
+    `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (with a `group`: its split update
+    around the group's all-reduce), pushed into the inference kernels device to device; `state_dict()` is rsl_rl's layout with either.
     `symmetry`: symmetry data augmentation inside the update of either learner - a `symmetry.SymmetryTables`, or the mirrors of this
     env's robot ("lr", "fb", "lr,fb" or a tuple of them), resolved with `symmetry.tables_for_env(env)`.
     `mirror_loss=c`, `data_augmentation=False` (with `symmetry`; forwarded to the learner): rsl_rl's mirror loss on the same tables, with
@@ -257,6 +257,8 @@ class Trainer:
             self.alg = PPO(self.policy, group=group, **ppo_kw)
         if group is not None:
             group.broadcast_parameters(self.policy)  # before the inference images are built from them
+            if learner == "hip":
+                self.alg.load_from(self.policy)  # ... and into the HIP learner's master parameters, which were copied before the broadcast
         lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
         host = lambda t: t.detach().cpu().numpy()  # noqa: E731
         self.actor = MlpPolicy([host(x.weight) for x in lin(self.policy.actor)], [host(x.bias) for x in lin(self.policy.actor)], "elu", device=str(self.device))

@@ -1,10 +1,11 @@
 """The HIP-native PPO learner (`include/rl_ppo.h`, `csrc/rl_ppo.hip`): `PPO.update` of `robot_lab_amd/ppo.py` without torch autograd.
 
-`ppo.PPO` stays the DEFINITION of the update rule (and the multi-GPU learner); `HipPPO` evaluates the same rule - clipped surrogate,
+`ppo.PPO` stays the DEFINITION of the update rule; `HipPPO` evaluates the same rule - clipped surrogate,
 clipped value loss, entropy bonus, KL-adaptive learning rate, gradient-norm clipping, Adam, the floor of std - with hand-written
 gfx950 kernels on fp32 master parameters that live on the device.  One `update()` enqueues `num_learning_epochs x num_mini_batches`
 mini-batches on the current stream and reads ONE small statistics block afterwards: no host synchronisation and no host decision
-inside the update (the learning rate is a device word).  Opt-in: `Trainer(env, learner="hip")`, `tools/train_demo.py --learner hip`.
+inside the update (the learning rate is a device word).  Opt-in: `Trainer(env, learner="hip")`, `tools/train_demo.py --learner hip`,
+`RL_LEARNER=hip` for the runner behind the reference's `train.py`.
 
     alg = HipPPO(policy)                 # same keywords as ppo.PPO; copies the ActorCritic's parameters to the device (`load_from`)
     stats = alg.update(storage, gen)     # same statistics keys as PPO.update; draws the permutation as PPO.update does
@@ -16,10 +17,22 @@ fused into the first layer's operand fetch and the loss head (`rl_ppo_set_symmet
 `HipPPO(policy, symmetry=tables, mirror_loss=c, data_augmentation=True | False)`: rsl_rl's mirror loss on the same tables, as `ppo.PPO`
 defines it (`rl_ppo_set_mirror_loss`); `update()` then returns `mirror_loss` too, read in the same one wait (`rl_ppo_stats_ex`).
 
+`HipPPO(policy, group=g)` (a `dist.LearnerGroup`, or anything with `world_size`, `enabled` and an in-place `all_reduce_sum(tensor)`): rsl_rl's
+multi-GPU contract.  The library holds no communicator: with an enabled group `update()` runs `rl_ppo_update_begin`, then per mini-batch
+`rl_ppo_minibatch_local` -> `group.all_reduce_sum(wire)` -> `rl_ppo_minibatch_apply`, all on the current stream, and reads the one statistics
+block afterwards.  The wire is the learner's flat gradient buffer adopted as a torch tensor, P gradient words and this rank's KL statistic in
+word [P]: ONE collective per mini-batch carries both (the torch learner uses two).  `apply` divides by the world in fp32, as `LearnerGroup`
+does.  Each rank draws its own permutation.  A disabled group (a world of one) or `None` takes the fused `rl_ppo_update`.
+
+    alg.optimizer_state_dict()           # the layout of torch.optim.Adam(policy.parameters()).state_dict(): loads into ppo.PPO's optimizer
+    alg.load_optimizer_state_dict(d)     # ... and back: a checkpoint written by either learner resumes the other
+    alg.policy                           # the ActorCritic a checkpoint stores (refresh it with `store_into(alg.policy)` before reading it)
+
 There is no CPU path and no fall-back to the torch learner: a missing library or an unsupported network raises."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 from .capi import PPO_EXPORTS, PPO_LIB, Batch, Hyper, RlPpoError, load_ppo_library  # noqa: F401  (the binding of include/rl_ppo.h)
 
@@ -44,6 +57,67 @@ def _network(seq, name):
     return [lin[0].in_features] + [m.out_features for m in lin], (kinds.pop() if kinds else "ELU")
 
 
+def parameter_shapes(actor_dims, critic_dims):
+    """shapes of `ActorCritic.parameters()` (= the flat layout of include/rl_ppo.h): std, then W, b per actor layer, then the critic's"""
+    shapes = [(actor_dims[-1],)]
+    for dims in (actor_dims, critic_dims):
+        for l in range(len(dims) - 1):
+            shapes += [(dims[l + 1], dims[l]), (dims[l + 1],)]
+    return shapes
+
+
+def adam_state_dict(shapes, exp_avg, exp_avg_sq, step, lr):
+    """`torch.optim.Adam(params, lr=lr).state_dict()` for parameters of `shapes`, from the flat moments, the common step count and the
+    learning rate.  step == 0: no state, as an optimiser that has not stepped."""
+    import torch
+
+    group = torch.optim.Adam([torch.zeros(1)], lr=float(lr)).state_dict()["param_groups"][0]  # the defaults of THIS torch
+    group["params"] = list(range(len(shapes)))
+    state, o = {}, 0
+    for i, shp in enumerate(shapes):
+        n = math.prod(shp)
+        if step > 0:
+            state[i] = dict(step=torch.tensor(float(step), dtype=torch.float32), exp_avg=exp_avg[o:o + n].reshape(shp).clone(),
+                            exp_avg_sq=exp_avg_sq[o:o + n].reshape(shp).clone())
+        o += n
+    if o != exp_avg.numel() or o != exp_avg_sq.numel():
+        raise ValueError(f"adam_state_dict: the moments hold {exp_avg.numel()} / {exp_avg_sq.numel()} entries, the shapes {o}")
+    return dict(state=state, param_groups=[group])
+
+
+def adam_state_flat(d, shapes):
+    """(exp_avg flat | None, exp_avg_sq flat | None, step, lr) of an Adam `state_dict()` over parameters of `shapes`; None moments: no state."""
+    import torch
+
+    groups = d["param_groups"]
+    if len(groups) != 1 or len(groups[0]["params"]) != len(shapes):
+        raise ValueError(f"optimizer state: expected one param group of {len(shapes)} parameters, got {[len(g['params']) for g in groups]}")
+    g = groups[0]
+    if tuple(g.get("betas", (0.9, 0.999))) != (0.9, 0.999) or g.get("eps", 1e-8) != 1e-8 or g.get("weight_decay", 0) or g.get("amsgrad") or g.get("maximize"):
+        raise ValueError("optimizer state: the HIP learner implements torch.optim.Adam's defaults only (betas, eps, no weight decay / amsgrad / maximize)")
+    state = d["state"]
+    if not state:
+        return None, None, 0, float(g["lr"])
+    m1, m2, steps = [], [], set()
+    for k, shp in zip(g["params"], shapes):
+        e = state[k]
+        if tuple(e["exp_avg"].shape) != tuple(shp) or tuple(e["exp_avg_sq"].shape) != tuple(shp):
+            raise ValueError(f"optimizer state: parameter {k} has moments of shape {tuple(e['exp_avg'].shape)}, the learner's is {tuple(shp)}")
+        m1.append(e["exp_avg"].reshape(-1))
+        m2.append(e["exp_avg_sq"].reshape(-1))
+        steps.add(int(float(e["step"])))
+    if len(steps) != 1:
+        raise ValueError(f"optimizer state: the parameters carry different step counts {sorted(steps)}: the HIP learner keeps one")
+    return torch.cat(m1), torch.cat(m2), steps.pop(), float(g["lr"])
+
+
+class _DevView:
+    """`__cuda_array_interface__` holder: lets torch adopt the learner's wire without copying (the handle owns the memory: `close()` drops the view)"""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = dict(shape=(int(count),), typestr="<f4", data=(int(ptr), False), version=2, strides=None)
+
+
 class HipPPO:
     """`ppo.PPO` on the HIP learner: same constructor keywords, same `update(storage, generator) -> dict`."""
 
@@ -54,9 +128,12 @@ class HipPPO:
 
         from .ppo import check_mirror_loss
 
-        if group is not None:
-            raise NotImplementedError("HipPPO is a single-GPU learner: the multi-GPU path (gradient all-reduce over a LearnerGroup) is the torch learner, "
+        if group is not None and not (isinstance(getattr(group, "world_size", None), int) and hasattr(group, "enabled") and callable(getattr(group, "all_reduce_sum", None))):
+            raise NotImplementedError(f"HipPPO: group={type(group).__name__} has no world_size / enabled / all_reduce_sum(tensor): the HIP learner's multi-GPU "
+                                      "path needs the SUM all-reduce of a robot_lab_amd.dist.LearnerGroup; any other gradient exchange is the torch learner, "
                                       "robot_lab_amd.ppo.PPO (Trainer(..., learner=\"torch\", group=...))")
+        if group is not None and group.enabled and group.world_size < 1:
+            raise ValueError(f"HipPPO: group.world_size={group.world_size} must be >= 1")
         if schedule not in ("adaptive", "fixed"):
             raise ValueError(f"HipPPO: unknown schedule {schedule!r} (\"adaptive\" or \"fixed\")")
         self._torch = torch
@@ -93,7 +170,10 @@ class HipPPO:
         self.value_loss_coef, self.use_clipped_value_loss, self.clip_param, self.entropy_coef = value_loss_coef, use_clipped_value_loss, clip_param, entropy_coef
         self.num_learning_epochs, self.num_mini_batches = num_learning_epochs, num_mini_batches
         self.learning_rate, self.schedule, self.desired_kl, self.max_grad_norm = learning_rate, schedule, desired_kl, max_grad_norm
-        self.group = None
+        self.group = group if group is not None and group.enabled else None  # a world of one: the fused rl_ppo_update, no collective
+        self._wire = None
+        self._opt_pending = None
+        self.policy = policy  # the module a checkpoint stores (`store_into(alg.policy)` refreshes it)
         self.device = std.device
         self.max_rows = int(max_rows_per_minibatch or 0)
         self._policy = policy
@@ -121,15 +201,20 @@ class HipPPO:
                                     int(max_rows), self.device.index or 0, C.byref(handle))
         self._check(rc)
         self.handle, self.max_rows = handle, int(max_rows)
-        if self.symmetry is not None:
-            try:
+        try:
+            if self.symmetry is not None:
                 self.set_symmetry(self.symmetry)
                 if self._mirror[0] is not None:
                     self.set_mirror_loss(*self._mirror)
-            except Exception:
-                self.close()  # never a learner that quietly runs without the symmetry it was asked for
-                raise
+            if self.group is not None:
+                self._set_world(self.group.world_size)
+        except Exception:
+            self.close()  # never a learner that quietly runs without the symmetry or the world it was asked for
+            raise
         self.num_parameters = int(self.lib.rl_ppo_num_parameters(self.handle))
+        if self._opt_pending is not None:
+            d, self._opt_pending = self._opt_pending, None
+            self.load_optimizer_state_dict(d)
         if self._policy is not None:
             self.load_from(self._policy)
             self._policy = None
@@ -159,6 +244,13 @@ class HipPPO:
             raise RlPpoError("HipPPO.set_mirror_loss before the handle exists: pass mirror_loss= to the constructor")
         self._check(self.lib.rl_ppo_set_mirror_loss(self.handle, float(coeff), int(bool(data_augmentation))))
         self.mirror_loss, self.data_augmentation = float(coeff), bool(data_augmentation)
+
+    def _set_world(self, world_size):
+        """`rl_ppo_set_world` + the wire adopted as a torch tensor (P + 1 floats of the learner's gradient buffer, no copy)"""
+        self._check(self.lib.rl_ppo_set_world(self.handle, int(world_size)))
+        ptr, cnt = C.c_void_p(), C.c_int64()
+        self._check(self.lib.rl_ppo_wire(self.handle, C.byref(ptr), C.byref(cnt)))
+        self._wire = self._torch.as_tensor(_DevView(ptr.value, cnt.value), device=self.device)
 
     def _need(self, rows):
         if self.handle is None:
@@ -233,6 +325,35 @@ class HipPPO:
         self._check(self.lib.rl_ppo_get_flat(self.handle, ["parameters", "gradients", "exp_avg", "exp_avg_sq"].index(which), C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    # -- optimiser state (checkpoints) -------------------------------------------------------------------------------------------
+    def optimizer_state_dict(self):
+        """The layout of `torch.optim.Adam(policy.parameters()).state_dict()`: per-parameter `step`, `exp_avg`, `exp_avg_sq` in
+        `ActorCritic.parameters()` order and `param_groups[0]["lr"]`.  One wait of the current stream."""
+        shapes = parameter_shapes(self.actor_dims, self.critic_dims)
+        if self.handle is None:  # no update yet: what was loaded, or an optimiser that has not stepped
+            zeros = self._torch.zeros(sum(math.prod(shp) for shp in shapes))
+            return self._opt_pending if self._opt_pending is not None else adam_state_dict(shapes, zeros, zeros, 0, self.learning_rate)
+        lr, step = C.c_double(), C.c_int64()
+        self._check(self.lib.rl_ppo_get_optimizer(self.handle, C.byref(lr), C.byref(step), self._stream()))
+        return adam_state_dict(shapes, self.flat("exp_avg"), self.flat("exp_avg_sq"), step.value, lr.value)
+
+    def load_optimizer_state_dict(self, d):
+        """An Adam `state_dict()` of this layout - written by this learner or by `ppo.PPO`'s optimizer - becomes the moments, the step counter and
+        the learning-rate word (stream-ordered).  A state without entries (an optimiser that never stepped) zeroes the moments."""
+        torch = self._torch
+        m1, m2, step, lr = adam_state_flat(d, parameter_shapes(self.actor_dims, self.critic_dims))
+        if self.handle is None:
+            self._opt_pending = d
+            self.learning_rate = lr
+            return
+        for which, m in ((2, m1), (3, m2)):
+            m = torch.zeros(self.num_parameters, device=self.device) if m is None else m.to(device=self.device, dtype=torch.float32).contiguous()
+            if m.numel() != self.num_parameters:
+                raise ValueError(f"optimizer state: {m.numel()} moment entries, the learner has {self.num_parameters} parameters")
+            self._check(self.lib.rl_ppo_set_flat(self.handle, which, C.c_void_p(m.data_ptr()), self._stream()))  # (on torch's current stream: a temporary `m` is safe)
+        self._check(self.lib.rl_ppo_set_optimizer(self.handle, lr, step, self._stream()))
+        self.learning_rate = lr
+
     # -- the update -----------------------------------------------------------------------------------------------------------------
     def _batch(self, storage):
         torch = self._torch
@@ -276,7 +397,22 @@ class HipPPO:
         perm = perm.to(device=self.device, dtype=torch.int64).contiguous()
         rows = perm.numel()
         self._need(rows // self.num_mini_batches)
-        self._check(self.lib.rl_ppo_update(self.handle, C.byref(b), C.c_void_p(perm.data_ptr()), rows, self._stream()))
+        if self.group is None:
+            self._check(self.lib.rl_ppo_update(self.handle, C.byref(b), C.c_void_p(perm.data_ptr()), rows, self._stream()))
+        else:  # the same sequence with the group's collective between the gradient and the step of every mini-batch; nothing waits on the host
+            mb, stream = rows // self.num_mini_batches, self._stream()
+            self._check(self.lib.rl_ppo_update_begin(self.handle, stream))
+            for _ in range(self.num_learning_epochs):
+                for i in range(self.num_mini_batches):
+                    self._check(self.lib.rl_ppo_minibatch_local(self.handle, C.byref(b), C.c_void_p(perm.data_ptr() + 8 * i * mb), mb, stream))
+                    try:
+                        self.group.all_reduce_sum(self._wire)
+                    except Exception as e:
+                        # the gradient of this mini-batch waits for a step that will not come, and the other ranks are past it: fail-stop
+                        self.close()
+                        raise RlPpoError(f"HipPPO.update: the group's all_reduce_sum failed in mini-batch {i} ({type(e).__name__}: {e}); the learner's "
+                                         "replicas can no longer be in step, so this learner is CLOSED - build a new one and load the last checkpoint") from e
+                    self._check(self.lib.rl_ppo_minibatch_apply(self.handle, stream))
         # the one wait of the update (keeps `keep` / `perm` alive until then)
         if self.mirror_loss is None:
             out = (C.c_double * 8)()
@@ -292,6 +428,7 @@ class HipPPO:
         return res
 
     def close(self):
+        self._wire = None  # (a view of the handle's memory)
         if getattr(self, "handle", None):
             self.lib.rl_ppo_destroy(self.handle)
             self.handle = None

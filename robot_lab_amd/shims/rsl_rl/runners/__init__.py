@@ -5,8 +5,9 @@
     policy = runner.get_inference_policy(device=...); runner.alg.policy  (exporters, `.reset(dones)`)
 
 `env` is the `RslRlVecEnvWrapper` of the shims around `robot_lab_amd.env.ManagerBasedRLEnv`.  Collection runs on the HIP kernels as
-one hipGraph launch per iteration (robot_lab_amd/collect.py), the update is robot_lab_amd/ppo.py, checkpoints use rsl_rl's layout
-(`model_<it>.pt`: model_state_dict / optimizer_state_dict / iter / infos)."""
+one hipGraph launch per iteration (robot_lab_amd/collect.py), the update is robot_lab_amd/ppo.py - or, with `RL_LEARNER=hip` in the
+environment, the HIP learner of robot_lab_amd/ppo_hip.py, on one GPU or under `--distributed` -, checkpoints use rsl_rl's layout
+(`model_<it>.pt`: model_state_dict / optimizer_state_dict / iter / infos) with either learner, and one learner's checkpoint resumes the other."""
 from __future__ import annotations
 
 import os
@@ -15,11 +16,20 @@ import time
 import torch
 
 
+def learner_from_env(environ=None) -> str:
+    """`RL_LEARNER=torch | hip` (default torch: robot_lab_amd.ppo.PPO); anything else is refused, never read as the default"""
+    value = (os.environ if environ is None else environ).get("RL_LEARNER", "torch")
+    if value not in ("torch", "hip"):
+        raise ValueError(f"RL_LEARNER={value!r}: the learner is \"torch\" (robot_lab_amd.ppo.PPO, the default) or \"hip\" (robot_lab_amd.ppo_hip.HipPPO)")
+    return value
+
+
 class OnPolicyRunner:
     def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device: str = "cpu"):
         from robot_lab_amd.ppo import Trainer
 
         self.env, self.cfg, self.log_dir, self.device = env, train_cfg, log_dir, device
+        self.learner = learner_from_env()
         pol, alg = dict(train_cfg.get("policy", {})), dict(train_cfg.get("algorithm", {}))
         if pol.get("class_name", "ActorCritic") != "ActorCritic" or alg.get("class_name", "PPO") != "PPO":
             raise NotImplementedError(f"stand-in runner: ActorCritic + PPO only, got {pol.get('class_name')} / {alg.get('class_name')}")
@@ -54,7 +64,7 @@ class OnPolicyRunner:
         self.trainer = Trainer(env.unwrapped, num_steps_per_env=int(train_cfg.get("num_steps_per_env", 24)), gamma=float(alg.get("gamma", 0.99)),
                                lam=float(alg.get("lam", 0.95)), seed=int(train_cfg.get("seed", 42)), actor_hidden=pol.get("actor_hidden_dims", (512, 256, 128)),
                                critic_hidden=pol.get("critic_hidden_dims", (512, 256, 128)), init_noise_std=float(pol.get("init_noise_std", 1.0)),
-                               clip_actions=getattr(env, "clip_actions", None), group=self.group if self.group.enabled else None,
+                               clip_actions=getattr(env, "clip_actions", None), group=self.group if self.group.enabled else None, learner=self.learner,
                                **{k: alg[k] for k in keys if k in alg})
         self.alg = self.trainer.alg
         self.alg.policy.reset = lambda dones=None: None  # feed-forward policy: nothing to reset (play.py:246)
@@ -108,15 +118,26 @@ class OnPolicyRunner:
             self._log_in_flight = None
         if self.log_dir and main:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+        if self.learner == "hip":
+            self.alg.store_into(self.alg.policy)  # `runner.alg.policy` is current after learn(), as the torch learner's is (exporters, play.py)
 
     def save(self, path: str, infos=None):
-        torch.save({"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(),
+        if self.learner == "hip":  # the master parameters and Adam's state live on the device: into the module / torch.optim.Adam's layout
+            self.alg.store_into(self.alg.policy)
+            optimizer_state = self.alg.optimizer_state_dict()
+        else:
+            optimizer_state = self.alg.optimizer.state_dict()
+        torch.save({"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": optimizer_state,
                     "iter": self.current_learning_iteration, "infos": infos}, path)
 
     def load(self, path: str, load_optimizer: bool = True, map_location=None):
         d = torch.load(path, map_location=map_location or self.trainer.device, weights_only=False)
         self.alg.policy.load_state_dict(d["model_state_dict"])
-        if load_optimizer and d.get("optimizer_state_dict"):
+        if self.learner == "hip":
+            self.alg.load_from(self.alg.policy)
+            if load_optimizer and d.get("optimizer_state_dict"):
+                self.alg.load_optimizer_state_dict(d["optimizer_state_dict"])
+        elif load_optimizer and d.get("optimizer_state_dict"):
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
         self.current_learning_iteration = int(d.get("iter", 0))
         self.trainer.push_parameters()

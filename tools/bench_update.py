@@ -19,7 +19,11 @@ time over n_sym x the HIP time of the "off" setting of the same run, when "off" 
 `--mirror-loss C`: every `--symmetry` entry other than "off" is timed three times - the augmentation alone, the augmentation + the mirror
 loss with coefficient C, the mirror loss alone (`data_augmentation=False`: only the actor sees the copies) - and each line carries
 `hip_over_off`, the HIP time as a multiple of the "off" setting's.
-    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...] [--mirror-loss C]"""
+`--split`: a third learner in the same alternation, "hip_split": `HipPPO(group=...)` with a world of ONE whose all-reduce does nothing - the
+host-driven rl_ppo_update_begin / rl_ppo_minibatch_local / rl_ppo_minibatch_apply sequence of a multi-GPU run without the collective, beside the
+fused `rl_ppo_update` ("hip").  `split_over_fused` is what the split itself costs: one more small launch per mini-batch and a host that
+issues every mini-batch through Python instead of running ahead inside one library call.
+    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...] [--mirror-loss C] [--split]"""
 import argparse
 import copy
 import json
@@ -66,7 +70,16 @@ def tables(env, spec, dims):
         return SymmetryTables(obs=rnd(dims[0]), critic=rnd(dims[1]), act=rnd(dims[2])), "random"
 
 
-def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_loss=None):
+class WorldOfOne:
+    """the group of `--split`: enabled, so that HipPPO takes the split sequence; one rank, so that there is nothing to reduce"""
+
+    world_size, enabled = 1, True
+
+    def all_reduce_sum(self, tensor):
+        return tensor
+
+
+def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_loss=None, split=False):
     env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
     tr = Trainer(env, seed=seed)
     tr.collector.collect()
@@ -78,7 +91,7 @@ def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_los
         if tab is not None and mirror_loss is not None:
             settings += [dict(mirror_loss=mirror_loss), dict(mirror_loss=mirror_loss, data_augmentation=False)]
         for kw in settings:
-            res = bench_one(tr, tab, repeat, warmup, seed, **kw)
+            res = bench_one(tr, tab, repeat, warmup, seed, split=split, **kw)
             res = dict(task=task, num_envs=num_envs, symmetry=spec, tables=kind, n_sym=tab.n_sym if tab else 1, **res)
             if mirror_loss is not None:
                 res.update(mirror_loss=kw.get("mirror_loss"), data_augmentation=kw.get("data_augmentation", True))
@@ -93,9 +106,11 @@ def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_los
     return out
 
 
-def bench_one(tr, tab, repeat, warmup, seed, **kw):
+def bench_one(tr, tab, repeat, warmup, seed, split=False, **kw):
     st = tr.storage
     learners = {"torch": PPO(copy.deepcopy(tr.policy), symmetry=tab, **kw), "hip": HipPPO(copy.deepcopy(tr.policy), symmetry=tab, **kw)}
+    if split:
+        learners["hip_split"] = HipPPO(copy.deepcopy(tr.policy), symmetry=tab, group=WorldOfOne(), **kw)
     gens = {k: torch.Generator(device="cuda:0").manual_seed(seed) for k in learners}
     times = {k: [] for k in learners}
     for it in range(warmup + repeat):
@@ -116,6 +131,9 @@ def bench_one(tr, tab, repeat, warmup, seed, **kw):
         med = statistics.median(t)
         res[k] = dict(median_ms=med, min_ms=min(t), max_ms=max(t), tflops_at_median=flops / med / 1e9)
     res["speedup_median"] = res["torch"]["median_ms"] / res["hip"]["median_ms"]
+    if split:
+        res["split_over_fused"] = res["hip_split"]["median_ms"] / res["hip"]["median_ms"]
+        learners["hip_split"].close()
     learners["hip"].close()
     return res
 
@@ -128,6 +146,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--symmetry", nargs="+", default=["off"], help="settings to time, each \"off\" or mirrors (lr | fb | lr,fb)")
     ap.add_argument("--mirror-loss", type=float, default=None, metavar="C", help="also time every symmetry setting with the mirror loss, with and without the augmentation")
+    ap.add_argument("--split", action="store_true", help="also time the begin / local / apply sequence of a multi-GPU run at a world of one")
     a = ap.parse_args()
     for spec in a.symmetry:
         if spec != "off":
@@ -135,7 +154,7 @@ def main():
     if len(a.num_envs) != len(a.task):
         ap.error("one --num-envs per --task")
     for task, n in zip(a.task, a.num_envs):
-        for res in bench(task, n, a.repeat, a.warmup, a.symmetry, mirror_loss=a.mirror_loss):
+        for res in bench(task, n, a.repeat, a.warmup, a.symmetry, mirror_loss=a.mirror_loss, split=a.split):
             print(json.dumps(res), flush=True)
 
 
