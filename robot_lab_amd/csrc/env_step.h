@@ -27,17 +27,26 @@
 //                     [wavefront][id] behind the reward-term rows (tools/phase_clock.py reads them): s_waitcnt 0, read the clock,
 //                     add the interval to the phase that ends, read the clock again - the bookkeeping itself is not counted.
 // The ids index tools/phase_clock.py PHASES.
+// The step kernels' clock starts at KERNEL ENTRY (RL_PHASE_ENTRY, rl_env_kernels.h env_kernel): phase `start` is everything in front of the
+// lane program's `load` - table staging, the staging barrier, the Uni / LdsPlan set-up, the log ring's reads, the action loads.
+// RL_PHASE_START(t) hands the entry stamp to the lane program, which exists only after the barrier.
+constexpr int RL_PHASE_ID_START = 25;
 #if defined(RL_PHASE_MARKS) && defined(__HIP_DEVICE_COMPILE__)
 #define RL_PHASE(id, name) asm volatile("; PHASE " name)
+#define RL_PHASE_ENTRY() asm volatile("; PHASE start")
 #elif defined(RL_PHASE_CLOCK) && defined(__HIP_DEVICE_COMPILE__)
 #define RL_PHASE(id, name) this->phase_stamp(id)
-#define RL_PHASE_START() (this->ph_t0 = 0, this->ph_cur = 0)  // (explicitly: round 4's tables carried a raw time stamp in the first row)
+#define RL_PHASE_ENTRY() const long long rl_phase_entry = (long long)__builtin_readcyclecounter()
+#define RL_PHASE_START(prog) ((prog).ph_t0 = rl_phase_entry, (prog).ph_cur = RL_PHASE_ID_START)
 #define RL_PHASE_CLOCK_ON 1
 #else
 #define RL_PHASE(id, name) ((void)0)
 #endif
 #ifndef RL_PHASE_START
-#define RL_PHASE_START() ((void)0)
+#define RL_PHASE_START(prog) ((void)0)
+#endif
+#ifndef RL_PHASE_ENTRY
+#define RL_PHASE_ENTRY() ((void)0)
 #endif
 constexpr int RL_PHASE_ROW0 = 24;   // first reward-term row the clock build borrows (A1 .. G1 tasks have <= 22 reward terms)
 constexpr int RL_PHASE_SLOTS = 32;
@@ -749,7 +758,7 @@ struct EnvLane {
   const KState& S;
   const TablesT<TP>& T;
   const LaneTabT<TP>& L;
-  const Uni u;
+  Uni u;  // (filled by setup(): the staged tables)
   int e, k, sub, li, Np;  // env, leg, sub-lane of the leg, lane index inside the env (k * SUB + sub)
   static constexpr int MAXOWN = SUB == 1 ? NBS : LaneTabT<TP>::template maxown<SUB>();
   int own[MAXOWN];        // body slots this lane updates every substep (all of them when a lane is a whole leg)
@@ -798,14 +807,31 @@ struct EnvLane {
   LsMat<LSS, NOWN, 3, GRAN> cf;      // [slot] (net contact force of the last substep, world; -)
   LsMat<LSS, NOWN, 3, GRAN> fric;    // [slot] (mu_s, mu_d, restitution; -)
 
-  RL_FN EnvLane(Ctx& c, const KState& s)
-      : ctx(c), S(s), T(c.template tables<TablesT<TP>>()), L(c.template tables<TablesT<TP>>().lane[c.k()]), u(make_uni(c, c.template tables<TablesT<TP>>())), tim{c.template lane_scratch<GRAN>() + LS::TIM * LSS, {}}, hist_n{c.template lane_scratch<GRAN>() + LS::HIST * LSS, {}},
+  // Two-part construction for the step kernels (rl_env_kernels.h env_kernel): the Deferred constructor takes what needs kernel arguments,
+  // tile and lane only - references, LDS addresses, the HBM state addresses - and can run BEFORE the table image is staged, so that
+  // load_early() issues under the staging; setup() reads the staged tables.
+  struct Deferred {};
+  RL_FN EnvLane(Ctx& c, const KState& s) : EnvLane(c, s, Deferred{}) { setup(); }
+  RL_FN EnvLane(Ctx& c, const KState& s, Deferred)
+      : ctx(c), S(s), T(c.template tables<TablesT<TP>>()), L(c.template tables<TablesT<TP>>().lane[c.k()]), tim{c.template lane_scratch<GRAN>() + LS::TIM * LSS, {}}, hist_n{c.template lane_scratch<GRAN>() + LS::HIST * LSS, {}},
         cf{c.template lane_scratch<GRAN>() + LS::CF * LSS, {}}, fric{c.template lane_scratch<GRAN>() + LS::FRIC * LSS, {}} {
     e = ctx.env();
     k = ctx.k();
     sub = ctx.sub();
     li = k * SUB + sub;
     Np = S.Npad;
+    if constexpr (STATE_BUF) {
+      lt_b = Ctx::state_buf(ctx.uniform_ptr(S.lane_state + (size_t)ctx.tile() * ((size_t)LY.NF_LANE * ROW)), (uint32_t)LY.NF_LANE * ROW * (uint32_t)sizeof(float));
+      et_b = Ctx::state_buf(ctx.uniform_ptr(S.env_state + (size_t)ctx.tile() * ((size_t)LY.NF_ENV * EPT)), (uint32_t)LY.NF_ENV * (uint32_t)EPT * (uint32_t)sizeof(float));
+      lt_off = (uint32_t)sizeof(float) * (uint32_t)(ctx.env_in_tile() * NLANE + k);
+      et_off = (uint32_t)sizeof(float) * (uint32_t)ctx.env_in_tile();
+    } else {
+      lt = S.lane_state + (size_t)ctx.tile() * ((size_t)LY.NF_LANE * ROW) + (uint32_t)(ctx.env_in_tile() * NLANE + k);
+      et = S.env_state + (size_t)ctx.tile() * ((size_t)LY.NF_ENV * EPT) + (uint32_t)ctx.env_in_tile();
+    }
+  }
+  RL_FN void setup() {
+    u = make_uni(ctx, T);
 #pragma unroll
     for (int i = 0; i < MAXOWN; ++i) {
       if constexpr (SUB == 8) own[i] = -1;
@@ -822,15 +848,6 @@ struct EnvLane {
       }
     }
     tim.set_own(own); hist_n.set_own(own); cf.set_own(own); fric.set_own(own);
-    if constexpr (STATE_BUF) {
-      lt_b = Ctx::state_buf(ctx.uniform_ptr(S.lane_state + (size_t)ctx.tile() * ((size_t)LY.NF_LANE * ROW)), (uint32_t)LY.NF_LANE * ROW * (uint32_t)sizeof(float));
-      et_b = Ctx::state_buf(ctx.uniform_ptr(S.env_state + (size_t)ctx.tile() * ((size_t)LY.NF_ENV * EPT)), (uint32_t)LY.NF_ENV * (uint32_t)EPT * (uint32_t)sizeof(float));
-      lt_off = (uint32_t)sizeof(float) * (uint32_t)(ctx.env_in_tile() * NLANE + k);
-      et_off = (uint32_t)sizeof(float) * (uint32_t)ctx.env_in_tile();
-    } else {
-      lt = S.lane_state + (size_t)ctx.tile() * ((size_t)LY.NF_LANE * ROW) + (uint32_t)(ctx.env_in_tile() * NLANE + k);
-      et = S.env_state + (size_t)ctx.tile() * ((size_t)LY.NF_ENV * EPT) + (uint32_t)ctx.env_in_tile();
-    }
   }
 #ifdef RL_PHASE_CLOCK_ON
   long long ph_t0 = 0;
@@ -888,7 +905,15 @@ struct EnvLane {
   RL_FN bool owns_slot(int s) const { return owns_group(L.slot_grp[s]); }
 
   // ------------------------------------------------------------------ load / store
+  // load() = load_early<true>() + load_late<2>().  The step kernels issue load_early() in front of the staging barrier - JOINTS: with the joint
+  // words, where the budget of loads in flight holds them (env_kernel EARLY) - and load_late<EARLY>() where load() stood.
+  static constexpr int EARLY_STATE_LOADS = 13 + 6 + 3 + (NW > 0 ? 3 : 0), EARLY_JOINT_LOADS = 5 * CL + 5 * NW;
   RL_FN void load() {
+    load_early<true>();
+    load_late<2>();
+  }
+  template <bool JOINTS>
+  RL_FN void load_early() {
     pos = {EF(LY.EF_ROOT + 0), EF(LY.EF_ROOT + 1), EF(LY.EF_ROOT + 2)};
     quat = {EF(LY.EF_ROOT + 3), EF(LY.EF_ROOT + 4), EF(LY.EF_ROOT + 5), EF(LY.EF_ROOT + 6)};
     vlin = {EF(LY.EF_ROOT + 7), EF(LY.EF_ROOT + 8), EF(LY.EF_ROOT + 9)};
@@ -898,6 +923,9 @@ struct EnvLane {
     base_com = {EF(LY.EF_BASE_COM + 0), EF(LY.EF_BASE_COM + 1), EF(LY.EF_BASE_COM + 2)};
     if (NW > 0) wr_com = {EF(LY.EF_WR_COM + 0), EF(LY.EF_WR_COM + 1), EF(LY.EF_WR_COM + 2)};
     else wr_com = base_com;  // quadrupeds: the wrench body is the root body
+    if constexpr (JOINTS) load_joints();
+  }
+  RL_FN void load_joints() {
 #pragma unroll
     for (int j = 0; j < CL; ++j) {
       q[j] = LF(LY.LF_Q + j);
@@ -914,6 +942,11 @@ struct EnvLane {
       kd[CL + i] = EF(LY.EF_TKD + i);
       act[CL + i] = EF(LY.EF_TACT + i);
     }
+  }
+  // EARLY: what load_early() took (0: nothing was issued early - callers use load(); 1: all but the joint words; 2: the joint words too)
+  template <int EARLY>
+  RL_FN void load_late() {
+    if constexpr (EARLY < 2) load_joints();
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       tau_app[j] = 0.f;

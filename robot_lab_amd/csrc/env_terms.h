@@ -368,6 +368,10 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
   float yaw_c, yaw_s;  // cos / sin of the heading
 
   RL_FN EnvProgram(Ctx& c, const KState& s) : Base(c, s) {}
+  using Deferred = typename Base::Deferred;
+  RL_FN EnvProgram(Ctx& c, const KState& s, Deferred d) : Base(c, s, d) {}
+  static constexpr int EARLY_ENV_LOADS = Base::EARLY_STATE_LOADS + 15;  // + the task words of load_task()
+  static constexpr int EARLY_JOINT_LOADS = Base::EARLY_JOINT_LOADS;
 
   RL_FN void load_task() {
     cmd = {this->EF(LY.EF_CMD + CMD_VX), this->EF(LY.EF_CMD + CMD_VY), this->EF(LY.EF_CMD + CMD_WZ)};
@@ -1450,8 +1454,10 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
   }
 
   // ---------------------------------------------------------------- step()
-  RL_FN void step() { step_front<false>(); }
-  RL_FN void step_head() { step_front<true>(); }
+  // EARLY: what the kernel issued in front of the staging barrier (EnvLane::load_late; > 0: load_task() is out too)
+  template <int EARLY = 0>
+  RL_FN void step() { step_front<false, EARLY>(); }
+  RL_FN void step_head() { step_front<true, 0>(); }
   // second launch of a split step: the state step_head() wrote back, its termination flags, then stages 6 - 9
   RL_FN void step_tail() {
     this->load();
@@ -1463,16 +1469,24 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
     step_back<true>(terminated, time_out, t_timeout, t_oob, terminated);
   }
 
-  template <bool HEAD>
+  template <bool HEAD, int EARLY>
   RL_FN void step_front() {
     // episode-log ring upkeep, by the first LOG_PARTS wavefronts of the launch: wavefront p keeps partial row p, lane l its word l
     // (a) the previous step's slot is final now: if that step reset nobody, it inherits its predecessor, so that every
     //     slot reads as "the log of the most recent step that reset an env" - what a caller of the reference sees, which
     //     rebuilds extras["log"] only inside _reset_idx [UPSTREAM B1];  (b) clear the next step's slot.
     // (whether the step reset anybody is the sum of its rows' LOG_FRESH words, which no copy touches: every wavefront reads the same
-    // answer whatever the others have written by then.)  Its reads go out HERE, in one batch with the state's; the writes follow the state loads.
+    // answer whatever the others have written by then.)  The reads stand in front of the late state loads and are waited for THERE, by the
+    // sum; the writes follow those loads.  What the compiler makes of the LOG_PARTS reads of a wave-uniform address: in the step kernels
+    // one batch of vector loads, summed as they arrive (behind the staging pins of env_kernel it does not turn them into scalar loads); in
+    // the reset / split-step kernels scalar loads, waited for in four groups of eight (profiles/launch_head_isa_listing.txt).  (Measured and
+    // dropped: ONE vector load - lane p reads row p's word - and a wave-level vote, first used behind the state loads: A1 Rough 4096 +0.03
+    // .. +0.06 us, G1 Rough 2048 +0.2 .. +0.4 us on top of the other head changes, profiles/launch_head_ab.txt.)
     constexpr size_t LOG_SLOT_WORDS = (size_t)LOG_PARTS * LOG_SIZE;
-    const int log_tl = ctx.tile(), log_wl = ctx.env_in_tile() * LPE + li;  // wavefront of the launch, lane of the wavefront
+    // (the wavefront's index through uniform_i: the keeper test is then a scalar branch.  As a vector compare it made an EXEC-masked region
+    // across the early state words in flight, and the register allocator parked live ones in its flow block, in front of the EXEC restore
+    // - tools/isa_exec_hazard.py refused that build)
+    const int log_tl = ctx.uniform_i(ctx.tile()), log_wl = ctx.env_in_tile() * LPE + li;  // wavefront of the launch, lane of the wavefront
     float* log_pv = S.log + (size_t)((S.step_counter - 1u) & (uint32_t)(LOG_RING - 1)) * LOG_SLOT_WORDS;
     const float* log_pp = S.log + (size_t)((S.step_counter - 2u) & (uint32_t)(LOG_RING - 1)) * LOG_SLOT_WORDS;
     float log_fresh = 0.f, log_word = 0.f;
@@ -1493,10 +1507,12 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
         a_in[j] = arow[TP::PAD && jid < 0 ? 0 : jid];
       }
     }
-    RL_PHASE_START();
     RL_PHASE(0, "load");
-    this->load();
-    load_task();  // same batch of HBM loads as the state: one round trip instead of a second one after the substeps
+    if constexpr (EARLY > 0) this->template load_late<EARLY>();  // (the rest, and load_task(), went out under the table staging)
+    else {
+      this->load();
+      load_task();  // same batch of HBM loads as the state: one round trip instead of a second one after the substeps
+    }
     rl_pin(a_in);
     if (log_tl < LOG_PARTS) {
       float* nx = S.log + (size_t)((S.step_counter + 1u) & (uint32_t)(LOG_RING - 1)) * LOG_SLOT_WORDS;

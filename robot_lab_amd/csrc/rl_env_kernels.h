@@ -305,12 +305,35 @@ __global__ __launch_bounds__(RL_LB(WGW)) void env_kernel(KState S, const void* _
   float* smem = reinterpret_cast<float*>(smem4);
   Tables* Tl = reinterpret_cast<Tables*>(smem);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  S.step_counter += *S.step_base;  // scalar load: the launch carries the offset from the device-side anchor (rl_env_graph_*)
-  {  // stage the used part of the table image into LDS (16-byte vectors): all loads in flight before the first LDS write
+  // The head of a STEP kernel (RESET == 0) is ordered around one memory round trip.  A wavefront is alone on its SIMD, so every dependent
+  // round trip in front of the substeps is idle time; the staging loads, the step offset and the state words whose addresses need nothing
+  // but kernel arguments, tile and lane (EnvLane::load_early) all issue before anything waits:
+  //   staging loads -> early state loads -> staging words into LDS (vmcnt counts the staging loads alone: they were issued first) ->
+  //   LDS-only barrier -> set-up from the staged tables -> the lane program, which consumes the early words where load() stood.
+  // The reset / split-step kernels keep the plain order (everything after the barrier): they are off the hot path.
+  constexpr int TPB = 64 * WGW;
+  constexpr int NIT = ((int)(sizeof(Tables) / 16) + TPB - 1) / TPB;
+  using Prog = EnvProgram<Ctx, TP, SP>;
+  // how much of the state goes out early: the staging loads + the early batch stay within what a wavefront can have in flight and still
+  // count (vmcnt is 6 bits; 60 leaves room for the step offset and the compiler's own): 2 - env words, task words and the joint words,
+  // 1 - without the joint words (the trunk + limbs instances, whose limbs carry more joints than the budget holds), 0 - nothing
+  constexpr int EARLY = RESET != 0 ? 0 : (NIT + Prog::EARLY_ENV_LOADS + Prog::EARLY_JOINT_LOADS <= 60 ? 2 : (NIT + Prog::EARLY_ENV_LOADS <= 60 ? 1 : 0));
+  uint32_t step_base = *S.step_base;  // scalar load: the launch carries the offset from the device-side anchor (rl_env_graph_*)
+  RL_PHASE_ENTRY();
+  const int TAB_F = (int)(S.table_bytes >> 2);
+  const int wtile = (int)blockIdx.x * WGW + wv, ntile = S.Npad / Ctx::EPT;
+  Ctx ctx;
+  ctx.T = Tl;
+  ctx.Tg = Tgv;
+  ctx.lscratch = smem + TAB_F + (WGW > 1 ? wv * wave_words : 0u);  // wave_words: LDS words of one wavefront behind the shared tables
+  // a padding wavefront of a four-wavefront workgroup (it returns behind the barrier) addresses the launch's last tile: its early loads
+  // stay inside the allocation, and nothing else of it touches memory
+  ctx.wtile = (WGW > 1 && wtile >= ntile) ? ntile - 1 : wtile;
+  ctx.lane = lane;
+  Prog prog(ctx, S, typename Prog::Deferred{});  // addresses only: nothing of the tables is read before the barrier
+  {  // stage the used part of the table image into LDS (16-byte vectors).  Step kernels: all loads in flight before the first LDS write (the pins below)
     const float4* src = reinterpret_cast<const float4*>(Tg);
     float4* dst = reinterpret_cast<float4*>(Tl);
-    constexpr int TPB = 64 * WGW;
-    constexpr int NIT = ((int)(sizeof(Tables) / 16) + TPB - 1) / TPB;
     const int n4 = (int)(S.table_bytes >> 4);
     float4 tmp[NIT];
 #pragma unroll
@@ -318,25 +341,46 @@ __global__ __launch_bounds__(RL_LB(WGW)) void env_kernel(KState S, const void* _
       const int i = (int)threadIdx.x + TPB * it;
       tmp[it] = src[i < n4 ? i : n4 - 1];  // unconditional (clamped) loads keep tmp[] in registers
     }
+    if constexpr (EARLY > 0) {
+      // (the scheduler otherwise moves the staging loads into the middle of the early batch, and their counted wait names half of it)
+      __builtin_amdgcn_sched_barrier(0);
+      prog.template load_early<EARLY == 2>();
+      prog.load_task();
+      rl_pin_uniform(step_base);  // the step offset is back before the barrier's wait, not fetched behind it
+    }
+    // The step kernels pin every loaded word HERE, between the two loops.  Without the pins the compiler sinks each clamped load into the
+    // branch that stores it: global_load_dwordx4 / s_waitcnt vmcnt(0) / ds_write_b128 three times over, one memory round trip after the
+    // other in front of everything else the wavefront does.  Pinned, the loads issue back to back and each store waits for its own
+    // (counted vmcnt).
+    if constexpr (RESET == 0) {
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) { rl_pin(tmp[it].x); rl_pin(tmp[it].y); rl_pin(tmp[it].z); rl_pin(tmp[it].w); }
+    }
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int i = (int)threadIdx.x + TPB * it;
-      if (i < n4) dst[i] = tmp[it];
+      // step kernels: the clamped store beside the clamped load - a lane beyond the image writes the image's last vector again, the same
+      // bits to the same address as its owner.  No EXEC-masked region stands between the early loads and the barrier that way.
+      if constexpr (RESET == 0) dst[i < n4 ? i : n4 - 1] = tmp[it];
+      else if (i < n4) dst[i] = tmp[it];
     }
   }
-  if (WGW > 1) __syncthreads();
-  else Ctx::wave_sync();
+  if (WGW > 1) {
+    if constexpr (EARLY > 0) {
+      // __syncthreads() is s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier: it would sit out the early loads.  The staging needs the LDS writes
+      // done (lgkmcnt), the barrier, and the compiler's accesses kept on their side of it (wave_sync's fence) - no vector-memory drain.
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) alone: vmcnt and expcnt at their maxima
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    } else __syncthreads();
+  } else Ctx::wave_sync();
+  if (WGW > 1 && wtile >= ntile) return;
+  S.step_counter += step_base;
   // LDS after the tables (only the staged bytes take room: the unused tail of the reward table is never touched): lds_plan above
-  const int TAB_F = (int)(S.table_bytes >> 2);
   const LdsPlan P = lds_plan<TP, SUB>(Tl->policy_dim, Tl->critic_dim, direct_group(*Tl, 0), direct_group(*Tl, 1), Tl->D, Tl->n_bodies, Tl->rew_ext_mask, Tl->n_rewards);
-  Ctx ctx;
-  ctx.T = Tl;
-  ctx.Tg = Tgv;
   ctx.dim[0] = Tl->policy_dim;
   ctx.dim[1] = Tl->critic_dim;
-  ctx.lscratch = smem + TAB_F + (WGW > 1 ? wv * wave_words : 0u);  // wave_words: LDS words of one wavefront behind the shared tables
-  ctx.wtile = (int)blockIdx.x * WGW + wv;
-  if (WGW > 1 && ctx.wtile >= S.Npad / Ctx::EPT) return;
   // limb-shared words (trunk + limbs instance): [kinematics block of every limb] [record block of every limb] [env words of every env]
   ctx.lbchain = ctx.lscratch + P.lb0 + (lane / SUB) * LbLayout<TP>::CHAINW;
   ctx.lbrec = ctx.lscratch + P.lbrec0 + (lane / SUB) * LbLayout<TP>::RECW;
@@ -349,14 +393,15 @@ __global__ __launch_bounds__(RL_LB(WGW)) void env_kernel(KState S, const void* _
   ctx.stage[0] = ctx.lscratch + P.stage0;
   ctx.stage[1] = ctx.lscratch + P.stage1;
   ctx.fstage = ctx.lscratch + P.fstage;
-  ctx.lane = lane;
-  EnvProgram<Ctx, TP, SP> prog(ctx, S);
+  prog.setup();  // what the lane program keeps of the staged tables: the uniform scalars, the lane's body slots
   if (RESET == 1)
     prog.reset_entry();  // (KMODE_RESET, and KMODE_STEP_TAIL: the second launch of a step split around the command-range decision)
   else if (RESET == 2)
     prog.step_head();    // KMODE_STEP_HEAD: the first launch of such a step
-  else
-    prog.step();
+  else {
+    RL_PHASE_START(prog);
+    prog.template step<EARLY>();
+  }
 }
 
 

@@ -17,9 +17,11 @@ namespace rl {
 #if defined(__HIP_DEVICE_COMPILE__)
 RL_FN void rl_pin(float& x) { asm volatile("" : "+v"(x)); }
 RL_FN void rl_pin(int& x) { asm volatile("" : "+v"(x)); }
+RL_FN void rl_pin_uniform(uint32_t& x) { asm volatile("" : "+s"(x)); }  // ... in its SCALAR register (a wave-uniform word, e.g. of a scalar load)
 #else
 RL_FN void rl_pin(float&) {}
 RL_FN void rl_pin(int&) {}
+RL_FN void rl_pin_uniform(uint32_t&) {}
 #endif
 template <int N>
 RL_FN void rl_pin(float (&a)[N]) {

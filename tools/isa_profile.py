@@ -2,7 +2,10 @@
 """Static profile of one kernel's gfx950 assembly (hipcc -save-temps .s): instruction classes per labelled block, loops
 (backward branches), and the `; PHASE <name>` markers the sources can plant with asm volatile("; PHASE x").
 
-    python tools/isa_profile.py kernel.s [--blocks]
+    python tools/isa_profile.py kernel.s [--blocks] [--head]
+
+--head: list what the kernel's head does with memory - every load, store, wait and barrier from the entry to the `; PHASE load` marker of
+a -DRL_PHASE_MARKS build (csrc/env_step.h), in program order: which loads are in flight together and which wait stands between them.
 """
 import re
 import sys
@@ -31,10 +34,29 @@ def classify(op):
     return "other"
 
 
+def head_listing(lines):
+    """memory instructions, waits and barriers up to the first `; PHASE load` (the first kernel of the file)"""
+    n = 0
+    for i, ln in enumerate(lines):
+        s = ln.strip()
+        if s.startswith("; PHASE load"):
+            break
+        if not s or s.startswith((";", ".")) or re.match(r"^(\.?[A-Za-z_][\w.$]*):", s):
+            continue
+        n += 1
+        op = s.split()[0]
+        if classify(op) in ("vmem", "smem", "lds", "waitcnt") or op.startswith("s_barrier"):
+            print(f"  {n:5d}  {s.split(';')[0].rstrip()}")
+    print(f"  ({n} instructions in front of `load`)")
+
+
 def main():
     path = sys.argv[1]
     show_blocks = "--blocks" in sys.argv
     lines = open(path).read().split("\n")
+    if "--head" in sys.argv:
+        head_listing(lines)
+        return
     label_line = {}
     blocks = OrderedDict()
     cur = "<entry>"

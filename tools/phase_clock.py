@@ -16,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robot_lab_amd.env import ManagerBasedRLEnv, _DevView  # noqa: E402
 
-PHASES = ['load', 'action', 'sub.actuators+kinematics', 'sub.contact_fetch', 'sub.link_records', 'sub.contact_pass1', 'sub.leg_sum', 'sub.crba', 'sub.schur', 'sub.aba', 'sub.cross_leg_sum', 'sub.trunk_solve', 'sub.back_subst', 'sub.contact_pass2', 'sub.sensor+integrate', 'terminations', 'rewards', 'rewards.terms', 'rewards.writeback', 'resets+commands+push', 'observations', 'obs.policy_done', 'obs.flush', 'store', 'end', 'rewards.term_body', 'reset.uniforms', 'reset.state', 'reset.log', 'commands', 'push', 'obs.kinematics']
+PHASES = ['load', 'action', 'sub.actuators+kinematics', 'sub.contact_fetch', 'sub.link_records', 'sub.contact_pass1', 'sub.leg_sum', 'sub.crba', 'sub.schur', 'sub.aba', 'sub.cross_leg_sum', 'sub.trunk_solve', 'sub.back_subst', 'sub.contact_pass2', 'sub.sensor+integrate', 'terminations', 'rewards', 'rewards.terms', 'rewards.writeback', 'resets+commands+push', 'observations', 'obs.policy_done', 'obs.flush', 'store', 'end', 'start', 'reset.uniforms', 'reset.state', 'reset.log', 'commands', 'push', 'obs.kinematics']
 ROW0, SLOTS = 24, 32
 
 # --reset-env0: the first env of EVERY wavefront times out on every counted step (its episode clock is set to the last step; the clock is
