@@ -37,6 +37,7 @@ extern "C" {
 #define RL_MAX_REWARD_TERMS 40
 #define RL_MAX_OBS_TERMS 12
 #define RL_TERM_NPARAM 8
+#define RL_MAX_OBS_HISTORY 32 /* longest observation history of a term (rl_env_set_obs_history) */
 
 /* ---- reward term kinds (each cites the reference function it restates) ------------------- */
 enum rl_reward_kind {
@@ -307,6 +308,9 @@ enum rl_buffer {
   RL_BUF_CMD_LEVELS = 24,  /* float [16]: current command ranges of the command_levels_* curricula - lin_vel_x lo/hi, lin_vel_y lo/hi,
                               ang_vel_z lo/hi (what the reference logs as Curriculum/command_levels_lin_vel = [1], _ang_vel = [5]),
                               then the accumulators of the running decision (sum, count per term) */
+  RL_BUF_OBS_POLICY_FRAME = 25, /* float [N, frame_dim]: the frame the last launch wrote - the policy row WITHOUT history.  An env without
+                                   observation history (rl_env_set_obs_history): the same pointer as RL_BUF_OBS_POLICY */
+  RL_BUF_OBS_CRITIC_FRAME = 26, /* likewise */
   RL_BUF_COUNT
 };
 
@@ -409,6 +413,28 @@ int32_t rl_env_num_envs(const rl_env* env);
 int32_t rl_env_num_actions(const rl_env* env);
 int32_t rl_env_obs_dim(const rl_env* env, int32_t group); /* 0 policy, 1 critic */
 int32_t rl_env_max_episode_length(const rl_env* env);
+
+/* ---- observation history: ObservationTermCfg.history_length / ObservationGroupCfg.history_length [UPSTREAM isaaclab.managers
+ * ObservationManager + isaaclab.utils.buffers CircularBuffer], flattened form -----------------------------------------------------
+ * per_term[k] = H_k, 0 <= H_k <= RL_MAX_OBS_HISTORY, one per term of the group (n = the group's term count; 0 policy, 1 critic).
+ * Legal once per group, after rl_env_create and before the first rl_env_reset / rl_env_step; afterwards, and inside a capture, it is
+ * refused with a reason.  An all-zero list allocates nothing and changes nothing.  It is NOT part of rl_env_desc: the descriptor, the
+ * table image, the step kernels and the Spec matching are what they are without it.
+ *   A FRAME of term k is its d_k values after noise, clip and scale - what the step kernel writes.  A term with H_k = 0 contributes
+ *   d_k columns (the current frame), one with H_k >= 1 contributes H_k * d_k: H_k frames, oldest first, newest last.  The group's row
+ *   is the term blocks in term order (term-major): [t0_oldest .. t0_newest, t1_oldest .. t1_newest, ...].
+ *   Every launch that writes a frame for an env pushes it ONCE into that env's history: rl_env_step, rl_env_reset with or without
+ *   env_ids (reset recomputes the observations of every env, so envs outside env_ids push one frame as well), the three-launch step
+ *   of the command_levels_* curricula.  An env the launch reset (step: terminated | time_out; reset: env_ids NULL or listed) gets all
+ *   H_k slots filled with its post-reset frame.
+ * A group with history gets a second ring [2][Npad][hist_dim] (zeroed), written by ONE launch for both groups that follows every
+ * frame-writing launch sequence on the same stream: it reads the frame slot t % 2 and the history slot (t - 1) % 2 and writes the
+ * history slot t % 2 - nothing is shifted in place, every pointer repeats with period 2, the capture protocol below is unchanged.
+ * RL_BUF_OBS_POLICY / _CRITIC, their _RING forms and rl_env_obs_dim then describe the history ring; RL_BUF_OBS_*_FRAME the frame.
+ * History is state carried between steps; rl_env_import_state leaves it alone (a caller saves / restores the current slot itself). */
+int rl_env_set_obs_history(rl_env* env, int32_t group, const int32_t* per_term, int32_t n);
+/* The lists: writes min(cap, term count) lengths into `out` (zeros when never set; out may be NULL), returns the group's term count. */
+int32_t rl_env_obs_history(const rl_env* env, int32_t group, int32_t* out, int32_t cap);
 /* Environments a 64-lane wavefront simulates: 4 (sixteen lanes per env - the latency mapping, what <= ~8 k quadruped envs per GPU and
  * every trunk + limbs robot get) or 16 (one lane per limb - the throughput mapping of large launches).  Chosen by rl_env_create from
  * the launch size (csrc/rl_env.hip envs_per_wave; RL_ENV_SUB=4|1 forces either); results do not depend on it beyond fp32 round-off.

@@ -21,6 +21,7 @@ EXPORTS = [
     "rl_env_import_state", "rl_env_read_log", "rl_env_log_slot", "rl_env_obs_slot", "rl_env_step_count", "rl_env_set_step_count", "rl_env_num_envs", "rl_env_num_actions", "rl_env_obs_dim", "rl_env_max_episode_length", "rl_env_envs_per_wavefront", "rl_env_spec_id", "rl_env_plan",
     "rl_env_spec_source", "rl_env_register_spec_plugin", "rl_env_spec_plugin_count", "rl_env_abi_stamp",
     "rl_env_destroy", "rl_env_last_error", "rl_env_desc_size", "rl_env_graph_begin", "rl_env_graph_end", "rl_env_graph_launching",
+    "rl_env_set_obs_history", "rl_env_obs_history",
 ]
 
 _libs: dict[str, C.CDLL] = {}
@@ -69,6 +70,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rl_env_abi_stamp.restype = C.c_char_p
     lib.rl_env_obs_dim.argtypes = [C.c_void_p, C.c_int32]
     lib.rl_env_obs_dim.restype = C.c_int32
+    if hasattr(lib, "rl_env_set_obs_history"):  # (absent from an RL_ENV_LIB build of an older tree - kernel A/Bs: such an env has no history, and asking for one raises)
+        lib.rl_env_set_obs_history.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+        lib.rl_env_obs_history.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+        lib.rl_env_obs_history.restype = C.c_int32
     lib.rl_env_destroy.argtypes = [C.c_void_p]
     lib.rl_env_last_error.restype = C.c_char_p
     lib.rl_env_desc_size.restype = C.c_uint64
@@ -99,7 +104,7 @@ class NativeEnv:
     library, host addresses for the CPU lane emulator used by the tests)."""
 
     def __init__(self, desc: EnvDesc, heights, terrain_origins, env_origins, num_envs: int, seed: int, device: int = 0,
-                 lib_path: str | None = None):
+                 lib_path: str | None = None, obs_history: dict | None = None):
         self.lib = load_library(lib_path)
         self.handle = C.c_void_p()
         keep = []
@@ -114,6 +119,30 @@ class NativeEnv:
         self.num_envs = num_envs
         self.num_actions = self.lib.rl_env_num_actions(self.handle)
         self.max_episode_length = self.lib.rl_env_max_episode_length(self.handle)
+        # observation history (`rl_env_set_obs_history`): {"policy": [H_0, ...], "critic": [...]} per-term lengths, applied here - before
+        # anybody fetches a buffer - and, because they are constructor arguments, again by whoever creates the env anew (the JIT path)
+        for group, name in enumerate(("policy", "critic")):
+            lengths = (obs_history or {}).get(name)
+            if lengths is not None and any(int(h) != 0 for h in lengths):
+                self.set_obs_history(group, lengths)
+
+    def set_obs_history(self, group: int, lengths):
+        if not hasattr(self.lib, "rl_env_set_obs_history"):
+            raise RlEnvError("this env library predates observation history (rl_env_set_obs_history): rebuild it")
+        arr = (C.c_int32 * len(lengths))(*[int(h) for h in lengths])
+        self._check(self.lib.rl_env_set_obs_history(self.handle, group, arr, len(lengths)))
+
+    def obs_history(self, group: int) -> list:
+        if not hasattr(self.lib, "rl_env_obs_history"):
+            return []
+        out = (C.c_int32 * 64)()
+        n = self.lib.rl_env_obs_history(self.handle, group, out, 64)
+        if n < 0:
+            raise RlEnvError("rl_env_obs_history failed")
+        return [int(out[i]) for i in range(n)]
+
+    def obs_dim(self, group: int) -> int:
+        return int(self.lib.rl_env_obs_dim(self.handle, group))
 
     def envs_per_wavefront(self) -> int:
         return int(self.lib.rl_env_envs_per_wavefront(self.handle))

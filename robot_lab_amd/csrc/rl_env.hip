@@ -58,6 +58,12 @@ extern "C" __attribute__((visibility("hidden"))) int rl_env_launch_sub8(const vo
 #endif
 RL_SPEC_LIST(RL_SPEC_DECL)
 #undef RL_SPEC_DECL
+// ... and of the observation-history launch (rl_env_history.hip: a translation unit that shares no header with the step kernels)
+#ifndef RL_ENV_SINGLE_TU
+extern "C" __attribute__((visibility("hidden"))) int rl_env_launch_history(const void* args, void* stream);
+#else
+#include "rl_env_history.hip"
+#endif
 #ifdef RL_ENV_SINGLE_TU
 #define RL_ENV_TU_SUB 1
 #include "rl_env_sub.inl"
@@ -269,6 +275,9 @@ struct Backend {
   int launch_u32(uint32_t* p, uint32_t v, int add, void* stream) {  // *p = v / *p += v, stream-ordered (capturable)
     hipLaunchKernelGGL(u32_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, p, v, add);
     return check(hipGetLastError());
+  }
+  int launch_history(const HistArgs& A, void* stream) {  // include/rl_env.h rl_env_set_obs_history: one launch for both groups
+    return check((hipError_t)rl_env_launch_history(&A, stream));
   }
   int launch_commit(const KState& S, const Tables* T, const AosPtrs& A, void* stream) {
     hipLaunchKernelGGL(commit_kernel, dim3((S.Npad + 63) / 64), dim3(64), 0, (hipStream_t)stream, S, T, A);

@@ -45,11 +45,15 @@ int rl_env_get_buffer(rl_env* env, int32_t which, void** dev_ptr, int64_t shape[
     return 0;
   };
   if ((which == RL_BUF_CONTACT_FORCE || which == RL_BUF_JOINT_TORQUE || which == RL_BUF_JOINT_ACC) && I.enable_inspection()) return -1;
+  // a group with observation history (rl_env_set_obs_history): OBS_* and OBS_*_RING are its history ring, OBS_*_FRAME the step kernel's frame
+  const bool hp = I.hist_dim[0] > 0, hc = I.hist_dim[1] > 0;
   switch (which) {
-    case RL_BUF_OBS_POLICY: return set(I.S.obs_policy, 2, N, I.tables.policy_dim, 1, FS);  // the slot the last step()/reset() wrote
-    case RL_BUF_OBS_CRITIC: return set(I.S.obs_critic, 2, N, I.tables.critic_dim, 1, FS);
-    case RL_BUF_OBS_POLICY_RING: return set(I.obs_ring[0][0], 3, 2, Np, I.tables.policy_dim, FS);
-    case RL_BUF_OBS_CRITIC_RING: return set(I.obs_ring[1][0], 3, 2, Np, I.tables.critic_dim, FS);
+    case RL_BUF_OBS_POLICY: return hp ? set(I.hist_ring[0][I.obs_slot], 2, N, I.hist_dim[0], 1, FS) : set(I.S.obs_policy, 2, N, I.tables.policy_dim, 1, FS);  // the slot the last step()/reset() wrote
+    case RL_BUF_OBS_CRITIC: return hc ? set(I.hist_ring[1][I.obs_slot], 2, N, I.hist_dim[1], 1, FS) : set(I.S.obs_critic, 2, N, I.tables.critic_dim, 1, FS);
+    case RL_BUF_OBS_POLICY_RING: return hp ? set(I.hist_ring[0][0], 3, 2, Np, I.hist_dim[0], FS) : set(I.obs_ring[0][0], 3, 2, Np, I.tables.policy_dim, FS);
+    case RL_BUF_OBS_CRITIC_RING: return hc ? set(I.hist_ring[1][0], 3, 2, Np, I.hist_dim[1], FS) : set(I.obs_ring[1][0], 3, 2, Np, I.tables.critic_dim, FS);
+    case RL_BUF_OBS_POLICY_FRAME: return set(I.S.obs_policy, 2, N, I.tables.policy_dim, 1, FS);
+    case RL_BUF_OBS_CRITIC_FRAME: return set(I.S.obs_critic, 2, N, I.tables.critic_dim, 1, FS);
     case RL_BUF_TASK_STATE: return set(I.task_state, 2, N, RL_TASK_STATE_NF, 1, FS);
     case RL_BUF_GAINS: return set(I.gains, 3, N, 2, D, FS);
     case RL_BUF_CMD_LEVELS: return set(I.S.cmd_levels, 1, rl::CL_WORDS, 1, 1, FS);
@@ -131,7 +135,19 @@ int32_t rl_env_num_envs(const rl_env* env) { return reinterpret_cast<const Impl*
 int32_t rl_env_num_actions(const rl_env* env) { return reinterpret_cast<const Impl*>(env)->D; }
 int32_t rl_env_obs_dim(const rl_env* env, int32_t group) {
   const Impl* I = reinterpret_cast<const Impl*>(env);
+  if ((group == 0 || group == 1) && I->hist_dim[group] > 0) return I->hist_dim[group];  // (rl_env_set_obs_history)
   return group == 0 ? I->tables.policy_dim : I->tables.critic_dim;
+}
+int rl_env_set_obs_history(rl_env* env, int32_t group, const int32_t* per_term, int32_t n) {
+  if (!env) return rl::fail("null env");
+  return reinterpret_cast<Impl*>(env)->set_obs_history(group, per_term, n);
+}
+int32_t rl_env_obs_history(const rl_env* env, int32_t group, int32_t* out, int32_t cap) {
+  if (!env || (group != 0 && group != 1)) return -1;
+  const Impl* I = reinterpret_cast<const Impl*>(env);
+  const int32_t n = I->obs_n_terms(group);
+  for (int32_t i = 0; out && i < n && i < cap; ++i) out[i] = i < (int32_t)I->hist_len[group].size() ? I->hist_len[group][i] : 0;
+  return n;
 }
 int32_t rl_env_max_episode_length(const rl_env* env) { return reinterpret_cast<const Impl*>(env)->tables.max_episode_length; }
 int32_t rl_env_envs_per_wavefront(const rl_env* env) { return reinterpret_cast<const Impl*>(env)->ept; }

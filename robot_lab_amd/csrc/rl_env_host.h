@@ -9,12 +9,20 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rl_env.h"
 #include "env_aos.h"
 #include "env_spec.h"
 #include "env_tables.h"
+// (holds no real-typed token, so the retyped fp64 copy of these sources - tests/emu/make_f64.py - takes it from the tree as it is)
+#if __has_include("env_history.h")
+#include "env_history.h"
+#else
+#include "../../../../../robot_lab_amd/csrc/env_history.h"
+#endif
 
 namespace rl {
 
@@ -28,6 +36,14 @@ inline int fail(const std::string& msg) {
   last_error() = msg;
   return -1;
 }
+
+static_assert(MAX_OBS_HISTORY == RL_MAX_OBS_HISTORY, "include/rl_env.h and csrc/env_history.h disagree");
+using HistArgs = HistArgsT<float>;  // the observation-history launch (csrc/env_history.h)
+// does the backend carry a kernel for it (the HIP library), or does the host run the shared per-element rule itself (the CPU lane emulator)?
+template <class B, class = void>
+struct has_history_launch : std::false_type {};
+template <class B>
+struct has_history_launch<B, std::void_t<decltype(std::declval<B&>().launch_history(std::declval<const HistArgs&>(), (void*)nullptr))>> : std::true_type {};
 
 inline int obs_term_dim(const rl_env_desc& d, int kind) {
   switch (kind) {
@@ -642,6 +658,13 @@ struct EnvImpl {
   // the two observation groups alternate between two HBM buffers (include/rl_env.h "Ownership"): obs_slot = the one last written
   float* obs_ring[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [group][slot]
   int obs_slot = 0;
+  // observation history (include/rl_env.h rl_env_set_obs_history): a second ring per group [2][Npad][hist_dim], filled by one launch
+  // after every frame-writing launch sequence; slot parity = obs_slot.  hist_dim 0: the group keeps none.
+  float* hist_ring[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [group][slot]
+  HistCol* hist_cols[2] = {nullptr, nullptr};
+  int hist_dim[2] = {0, 0};
+  std::vector<int32_t> hist_len[2];  // per term; empty: never set
+  bool hist_set[2] = {false, false}, started = false;  // started: a reset / step has been launched
   bool alloc_failed = false;
   uint8_t* reset_mask = nullptr;
   float* terrain_dev = nullptr;
@@ -906,7 +929,9 @@ struct EnvImpl {
     }
     flip_obs(s);
     s.mode = KMODE_RESET;
-    return be.launch(s, packed_dev, inst, stream) ? fail("launch failed: " + be.error()) : 0;
+    started = true;
+    if (be.launch(s, packed_dev, inst, stream)) return fail("launch failed: " + be.error());
+    return push_history(s.reset_mask, nullptr, env_ids == nullptr, stream);
   }
 
   int step(const float* action_dev, void* stream, const float* ro_values = nullptr, float* ro_rewards = nullptr, uint8_t* ro_dones = nullptr,
@@ -917,11 +942,13 @@ struct EnvImpl {
     KState s = S;
     s.step_counter = ++step_counter - anchor;
     flip_obs(s);
+    started = true;
     s.action_in = action_dev;
     s.ro_values = ro_values; s.ro_rewards = ro_rewards; s.ro_dones = ro_dones; s.ro_gamma = ro_gamma;
     if (!(tables.cur_lin || tables.cur_ang)) {
       s.mode = KMODE_STEP;
-      return be.launch(s, packed_dev, inst, stream) ? fail("launch failed: " + be.error()) : 0;
+      if (be.launch(s, packed_dev, inst, stream)) return fail("launch failed: " + be.error());
+      return push_history(S.terminated, S.time_out, false, stream);
     }
     // command_levels_* curricula (VEL/mdp/curriculums.py:21-94): the decision of a step whose counter is a multiple of the episode
     // length is a reduction over every env that step resets, and the reference takes it FIRST inside _reset_idx - the commands those
@@ -934,7 +961,71 @@ struct EnvImpl {
     if (be.launch_cmd_levels(S.cmd_levels, cmd_level_params, S.step_base, step_counter - anchor, (uint32_t)tables.max_episode_length, stream))
       return fail("launch failed: " + be.error());
     s.mode = KMODE_STEP_TAIL;
-    return be.launch(s, packed_dev, inst, stream) ? fail("launch failed: " + be.error()) : 0;
+    if (be.launch(s, packed_dev, inst, stream)) return fail("launch failed: " + be.error());
+    return push_history(S.terminated, S.time_out, false, stream);
+  }
+
+  // ---- observation history (include/rl_env.h rl_env_set_obs_history; csrc/env_history.h has the rule) ----------------------------
+  int obs_n_terms(int group) const { return group == 0 ? tables.n_policy : tables.n_critic; }
+  int obs_frame_dim(int group) const { return group == 0 ? tables.policy_dim : tables.critic_dim; }
+  int set_obs_history(int group, const int32_t* per_term, int32_t n) {
+    if (group != 0 && group != 1) return fail("rl_env_set_obs_history: group must be 0 (policy) or 1 (critic)");
+    if (capturing) return fail("rl_env_set_obs_history inside a capture");
+    if (started) return fail("rl_env_set_obs_history after the first rl_env_reset / rl_env_step: the history length is fixed before the env runs");
+    if (hist_set[group]) return fail(std::string("rl_env_set_obs_history: the history of the ") + (group == 0 ? "policy" : "critic") + " group was already set (once per group)");
+    if (n != obs_n_terms(group) || (n > 0 && !per_term))
+      return fail("rl_env_set_obs_history: " + std::to_string(n) + " lengths for a group of " + std::to_string(obs_n_terms(group)) + " terms");
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+      if (per_term[i] < 0 || per_term[i] > RL_MAX_OBS_HISTORY)
+        return fail("rl_env_set_obs_history: history length " + std::to_string(per_term[i]) + " of term " + std::to_string(i) + " outside 0.." + std::to_string(RL_MAX_OBS_HISTORY));
+      any = any || per_term[i] > 0;
+    }
+    if (any) {
+      std::vector<int32_t> dims(n);
+      const rl_obs_term* src = group == 0 ? desc.task.policy : desc.task.critic;
+      for (int i = 0; i < n; ++i) dims[i] = obs_term_dim(desc, src[i].kind);
+      const int32_t hd = history_columns(dims.data(), per_term, n, nullptr);
+      // the launch indexes the elements of both groups with 32 bits
+      const uint64_t other = (uint64_t)N * (uint64_t)hist_dim[group ^ 1];
+      if ((uint64_t)N * (uint64_t)hd + other > 0xffff0000ull) return fail("rl_env_set_obs_history: num_envs x history row exceeds 2^32 elements");
+      if (be.activate()) return fail("device activation failed: " + be.error());
+      std::vector<HistCol> cols(hd);
+      history_columns(dims.data(), per_term, n, cols.data());
+      const size_t row = (size_t)Npad * (size_t)hd;
+      float* ring = alloc<float>(2 * row);  // zeroed: rows N..Npad stay zero, and so does a slot nothing has been pushed into
+      HistCol* cd = alloc<HistCol>(hd);
+      if (!ring || !cd) return fail("device allocation failed: " + be.error());
+      be.h2d(cd, cols.data(), cols.size() * sizeof(HistCol));
+      hist_ring[group][0] = ring; hist_ring[group][1] = ring + row;
+      hist_cols[group] = cd;
+      hist_dim[group] = hd;
+    }
+    hist_len[group].assign(per_term, per_term + n);
+    hist_set[group] = true;
+    return 0;
+  }
+  // one launch for both groups after a frame-writing launch sequence: frame slot t % 2 + history slot (t - 1) % 2 -> history slot t % 2
+  int push_history(const uint8_t* r0, const uint8_t* r1, bool all, void* stream) {
+    if (hist_dim[0] == 0 && hist_dim[1] == 0) return 0;
+    HistArgs A{};
+    for (int g = 0; g < 2; ++g) {
+      A.g[g].frame = obs_ring[g][obs_slot];
+      A.g[g].prev = hist_ring[g][obs_slot ^ 1];
+      A.g[g].out = hist_ring[g][obs_slot];
+      A.g[g].cols = hist_cols[g];
+      A.g[g].frame_dim = obs_frame_dim(g);
+      A.g[g].hist_dim = hist_dim[g];
+    }
+    A.n0 = (uint32_t)N * (uint32_t)hist_dim[0];
+    A.total = A.n0 + (uint32_t)N * (uint32_t)hist_dim[1];
+    A.r0 = r0; A.r1 = r1; A.reset_all = all ? 1 : 0;
+    if constexpr (has_history_launch<Backend>::value) {
+      if (be.launch_history(A, stream)) return fail("history launch failed: " + be.error());
+    } else {  // no kernel in this backend (the CPU lane emulator): the same per-element rule, in a plain loop over host memory
+      for (uint32_t i = 0; i < A.total; ++i) history_element(A, i);
+    }
+    return 0;
   }
 
   // include/rl_env.h "hipGraph capture of a loop around rl_env_step"

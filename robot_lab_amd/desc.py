@@ -22,6 +22,7 @@ RL_MAX_SELF_PAIRS = 80
 RL_MAX_REWARD_TERMS = 40
 RL_MAX_OBS_TERMS = 12
 RL_TERM_NPARAM = 8
+RL_MAX_OBS_HISTORY = 32
 RL_LOG_SIZE = 64
 RL_LOG_RING = 64
 RL_LOG_PARTS = 32  # partial rows of a ring slot (include/rl_env.h RL_BUF_LOG): a reader sums them
@@ -48,7 +49,7 @@ BUF = dict(
     OBS_POLICY=0, OBS_CRITIC=1, REWARD=2, TERMINATED=3, TIME_OUT=4, EPISODE_LENGTH=5, ROOT_STATE=6,
     JOINT_POS=7, JOINT_VEL=8, REWARD_TERMS=9, EPISODE_SUMS=10, COMMAND=11, CONTACT_FORCE=12,
     CONTACT_TIMERS=13, LOG=14, ACTION=15, JOINT_TORQUE=16, JOINT_ACC=17, ENV_ORIGIN=18, TERRAIN_LEVEL=19,
-    TASK_STATE=20, GAINS=21, OBS_POLICY_RING=22, OBS_CRITIC_RING=23, CMD_LEVELS=24,
+    TASK_STATE=20, GAINS=21, OBS_POLICY_RING=22, OBS_CRITIC_RING=23, CMD_LEVELS=24, OBS_POLICY_FRAME=25, OBS_CRITIC_FRAME=26,
 )
 # fields of one RL_BUF_TASK_STATE row (include/rl_env.h rl_task_state_field)
 TASK_STATE = dict(CMD=slice(0, 3), HEADING_TARGET=3, CMD_TIME_LEFT=4, METRIC_XY=5, METRIC_YAW=6, PUSH_TIME_LEFT=7,
@@ -173,12 +174,23 @@ class EnvDesc(C.Structure):
     body_names: list
     reward_names: list
 
-    def obs_dim(self, group: int) -> int:
+    def obs_term_dims(self, group: int) -> list:
+        """frame width of every term of a group (0 policy, 1 critic), in term order"""
         t = self.task
         terms, n = (t.policy, t.n_policy) if group == 0 else (t.critic, t.n_critic)
         D = self.model.num_dof
         dims = {0: 3, 1: 3, 2: 3, 3: 3, 4: D, 5: D, 6: D, 7: t.scan_nx * t.scan_ny, 8: D}
-        return int(sum(dims[terms[i].kind] for i in range(n)))
+        return [int(dims[terms[i].kind]) for i in range(n)]
+
+    def obs_dim(self, group: int, history=None) -> int:
+        """width of a group's row; `history`: per-term history lengths (include/rl_env.h rl_env_set_obs_history) - a term with
+        H >= 1 contributes H frames, one with H = 0 the current frame"""
+        dims = self.obs_term_dims(group)
+        if history is None:
+            return int(sum(dims))
+        if len(history) != len(dims):
+            raise ValueError(f"{len(history)} history lengths for a group of {len(dims)} terms")
+        return int(sum(d * max(1, int(h)) for d, h in zip(dims, history)))
 
 
 def _to_py(obj):

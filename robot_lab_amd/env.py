@@ -228,6 +228,25 @@ class _RewardManager:
         return {n: e._bufs["EPISODE_SUMS"][i, : e.num_envs] for i, n in enumerate(self.active_terms)}
 
 
+def resolve_obs_history(desc, obs_history) -> dict | None:
+    """`obs_history=` of the constructor -> per-term lists {"policy": [...], "critic": [...]}: a group's value is one length for every
+    term of the group (`{"policy": 5}`, IsaacLab's group-level `history_length`) or a list with one length per term."""
+    if not obs_history:
+        return None
+    out = {}
+    for name, val in dict(obs_history).items():
+        if name not in ("policy", "critic"):
+            raise ValueError(f"obs_history: unknown observation group {name!r} (policy, critic)")
+        n = int(desc.task.n_policy if name == "policy" else desc.task.n_critic)
+        lengths = [int(val)] * n if isinstance(val, (int, np.integer)) else [int(h) for h in val]
+        if len(lengths) != n:
+            raise ValueError(f"obs_history[{name!r}]: {len(lengths)} lengths for a group of {n} terms")
+        if any(h < 0 for h in lengths):
+            raise ValueError(f"obs_history[{name!r}]: negative history length in {lengths}")
+        out[name] = lengths
+    return out
+
+
 class ManagerBasedRLEnv(_EnvBase):
     """MI355X-native vectorised velocity-tracking environment.  See module docstring."""
 
@@ -236,7 +255,7 @@ class ManagerBasedRLEnv(_EnvBase):
 
     def __init__(self, cfg=None, render_mode=None, *, desc: EnvDesc | None = None, extra: dict | None = None,
                  num_envs: int | None = None, seed: int | None = None, device: str | None = None, terrain_seed: int = 0,
-                 lib_path: str | None = None, inspection: bool = False, specialise: bool | None = None, **kwargs):
+                 lib_path: str | None = None, inspection: bool = False, specialise: bool | None = None, obs_history: dict | None = None, **kwargs):
         self._task_name = cfg if isinstance(cfg, str) else (type(cfg).__name__ if cfg is not None else "task")
         if isinstance(cfg, str):  # a compiled descriptor bundle id / path (robot_lab_amd/data)
             desc, extra = load_bundle(cfg)
@@ -245,6 +264,8 @@ class ManagerBasedRLEnv(_EnvBase):
             from .model.cfg_compile import compile_cfg
             desc, spec = compile_cfg(cfg)
             extra = dict(terrain_generator=spec.get("terrain_generator"), env_spacing=spec.get("env_spacing"))
+            if obs_history is None:  # the cfg's history_length / flatten_history_dim, resolved per term (model/cfg_compile.py)
+                obs_history = spec.get("obs_history")
             num_envs = num_envs or cfg.scene.num_envs
             device = device or getattr(cfg.sim, "device", None)
             seed = seed if seed is not None else getattr(cfg, "seed", None)
@@ -252,6 +273,7 @@ class ManagerBasedRLEnv(_EnvBase):
             raise ValueError("ManagerBasedRLEnv needs a task cfg, a descriptor bundle id, or desc=")
         self.cfg = cfg
         self.desc = desc
+        hist = resolve_obs_history(desc, obs_history)
         self.render_mode = render_mode
         self.num_envs = int(num_envs or 4096)
         self._seed = 42 if seed is None else int(seed)
@@ -269,7 +291,7 @@ class ManagerBasedRLEnv(_EnvBase):
         self._dev_index = torch.device(self.device).index
         heights, terrain_origins, env_origins = build_world(desc, extra or {}, self.num_envs, terrain_seed)
         with torch.cuda.device(self._dev_index):
-            self._native = NativeEnv(desc, heights, terrain_origins, env_origins, self.num_envs, self._seed, self._dev_index, lib_path)
+            self._native = NativeEnv(desc, heights, terrain_origins, env_origins, self.num_envs, self._seed, self._dev_index, lib_path, obs_history=hist)
             # `specialise` (None: RL_ENV_JIT, default on): a task the library has no specialised step kernel for gets one compiled now - or loaded from
             # the cache - and the env is created again on it (robot_lab_amd/jit.py; any failure there: one log line and this interpreter env)
             from . import jit
@@ -277,7 +299,7 @@ class ManagerBasedRLEnv(_EnvBase):
             if jit.enabled(specialise) and self._native.spec_id() == 0 and os.environ.get("RL_ENV_SPEC", "1") != "0":
                 if jit.specialise(self._native.lib, desc, os.path.basename(str(self._task_name)), 16 // max(1, self._native.envs_per_wavefront())):
                     self._native.close()
-                    self._native = NativeEnv(desc, heights, terrain_origins, env_origins, self.num_envs, self._seed, self._dev_index, lib_path)
+                    self._native = NativeEnv(desc, heights, terrain_origins, env_origins, self.num_envs, self._seed, self._dev_index, lib_path, obs_history=hist)
         self.num_actions = self._native.num_actions
         self.max_episode_length = self._native.max_episode_length
         self.max_episode_length_s = float(desc.task.episode_length_s)
@@ -378,6 +400,17 @@ class ManagerBasedRLEnv(_EnvBase):
     def get_observations(self):
         return self._obs
 
+    def get_observation_frames(self) -> dict:
+        """The frames the last step() / reset() wrote, [N, frame_dim] per group (`RL_BUF_OBS_*_FRAME`): the rows WITHOUT observation
+        history.  Views, valid until step t + 2 like the observations; for an env without history they are the observations."""
+        if not self.obs_history:
+            return self._obs
+        out = {}
+        for name in ("policy", "critic"):
+            ptr, shape, dt = self._native.buffer(f"OBS_{name.upper()}_FRAME")
+            out[name] = torch.as_tensor(_DevView(ptr, shape, dt, self._native), device=self.device)
+        return out
+
     # -- hipGraph capture of a loop around step() (include/rl_env.h; robot_lab_amd/collect.py drives it) -------------------
     def _fill_live_logs(self):
         for _, ref in self._live_logs:
@@ -419,8 +452,21 @@ class ManagerBasedRLEnv(_EnvBase):
 
     def __repr__(self):
         lanes = 64 // max(1, self._native.envs_per_wavefront()) if getattr(self, "_native", None) is not None else 0
+        hist = self.obs_history if getattr(self, "_native", None) is not None else None
+        hist = f" obs_history={hist}" if hist else ""
         return (f"<robot_lab_amd ManagerBasedRLEnv num_envs={self.num_envs} device={self.device} actions={self.num_actions} "
-                f"step_kernel={self.step_kernel} lanes_per_env={lanes}>")
+                f"step_kernel={self.step_kernel} lanes_per_env={lanes}{hist}>")
+
+    @property
+    def obs_history(self) -> dict:
+        """Per-term observation history lengths of the groups that keep one (`rl_env_set_obs_history`): {} for an env without history,
+        else e.g. {"policy": [5, 5, 5, 5, 5, 5]}.  A group's row is then term-major, each term's frames oldest first."""
+        out = {}
+        for g, name in enumerate(("policy", "critic")):
+            lengths = self._native.obs_history(g)
+            if any(lengths):
+                out[name] = lengths
+        return out
 
     def close(self):
         if getattr(self, "_native", None) is not None:
@@ -479,6 +525,8 @@ class ManagerBasedRLEnv(_EnvBase):
         out["episode_sums"] = self._bufs["EPISODE_SUMS"][:, : self.num_envs].cpu().numpy().copy()
         out["terrain_level"] = self._bufs["TERRAIN_LEVEL"].cpu().numpy().copy()
         out["step_count"] = self._native.step_count
+        for name in self.obs_history:  # history is carried state: the current slot [N, hist_dim]
+            out["obs_history_" + name] = self._obs[name].cpu().numpy().copy()
         return out
 
     def load_state(self, state: dict):
@@ -499,6 +547,9 @@ class ManagerBasedRLEnv(_EnvBase):
             self.common_step_counter = int(state["step_count"])
         self._native.commit_state(self._stream())
         self._export_stamp = -1
+        for name in self.obs_history:
+            if "obs_history_" + name in state:
+                self._obs[name].copy_(torch.as_tensor(np.asarray(state["obs_history_" + name], dtype=np.float32), device=self.device).reshape(self._obs[name].shape))
 
     def write_state(self, root_state=None, joint_pos=None, joint_vel=None):
         """Overwrite root / joint state from host arrays (`rl_env_import_state`: export, overwrite, commit)."""

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import os
 
-from ..desc import OBS, REW, EnvDesc
+from ..desc import OBS, REW, RL_MAX_OBS_HISTORY, EnvDesc
 from .build import build_desc
 from .urdf import load_urdf
 
@@ -40,6 +40,33 @@ def _names(entity, key):
     if v is None:
         return None
     return [v] if isinstance(v, str) else list(v)
+
+
+def compile_obs_history(observations) -> dict:
+    """`history_length` / `flatten_history_dim` of the observation groups and terms [UPSTREAM isaaclab.managers ObservationManager]
+    -> {"policy": [H_0, ...], "critic": [...]}, one length per active term in term order.  A group's `history_length`, when not
+    None, replaces every term's, and its `flatten_history_dim` then replaces theirs.  Not part of the descriptor: the env applies the
+    lists through `rl_env_set_obs_history` (include/rl_env.h).  Only the flattened form is built; the other one is refused."""
+    history = {}
+    for gname in ("policy", "critic"):
+        grp = getattr(observations, gname, None)
+        history[gname] = []
+        if grp is None:
+            continue
+        g_hist = getattr(grp, "history_length", None)
+        for name, t in _terms(grp):
+            h = g_hist if g_hist is not None else getattr(t, "history_length", 0)
+            flat = getattr(grp, "flatten_history_dim", True) if g_hist is not None else getattr(t, "flatten_history_dim", True)
+            h = 0 if h is None else h
+            if isinstance(h, bool) or not isinstance(h, int) or h < 0:
+                raise UnsupportedTerm(f"observation term {gname}.{name}: history_length {h!r} (a non-negative integer)")
+            if h > RL_MAX_OBS_HISTORY:
+                raise UnsupportedTerm(f"observation term {gname}.{name}: history_length {h} exceeds {RL_MAX_OBS_HISTORY}")
+            if h > 0 and not flat:
+                raise UnsupportedTerm(f"observation term {gname}.{name}: history_length {h} with flatten_history_dim=False - only the flattened "
+                                      "history (the frames of a term side by side in the group's row) is built")
+            history[gname].append(h)
+    return history
 
 
 def compile_spec(cfg) -> tuple[dict, str]:
@@ -138,6 +165,7 @@ def compile_spec(cfg) -> tuple[dict, str]:
                 terms.append(e)
         obs[gname] = dict(terms=terms, enable_corruption=bool(getattr(grp, "enable_corruption", False)))
     task["observations"] = obs
+    spec["obs_history"] = compile_obs_history(cfg.observations)
     hs = getattr(cfg.scene, "height_scanner", None)
     if hs is not None:
         # the ray caster rides on the body its prim_path names (velocity_env_cfg.py:71; G1 moves it to

@@ -215,6 +215,9 @@ def mirror_repr(alg):
     return f", mirror_loss={alg.mirror_loss:g}" + ("" if alg.data_augmentation else ", data_augmentation=False")
 
 
+MAX_INPUT_WIDTH = 512  # = RL_MLP_MAX_WIDTH (include/rl_policy.h) = RL_PPO_MAX_WIDTH (include/rl_ppo.h): widest layer, the input included
+
+
 class Trainer:
     """collect (HIP, one graph launch) -> update -> push parameters, repeated: `OnPolicyRunner.learn` in miniature.
     `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (with a `group`: its split update
@@ -232,6 +235,12 @@ class Trainer:
 
         obs, _ = env.reset()
         od, cd, A = obs["policy"].shape[1], obs["critic"].shape[1], env.num_actions
+        for name, width in (("policy", od), ("critic", cd)):  # before anything is built: the kernels would fail deep inside otherwise
+            if width > MAX_INPUT_WIDTH:
+                hist = (getattr(env, "obs_history", None) or {}).get(name)
+                raise ValueError(f"Trainer: the {name} observation row is {width} columns wide" + (f" (observation history {hist})" if hist else "") +
+                                 f", the fused inference kernels and the HIP learner take at most {MAX_INPUT_WIDTH} input columns: shorten the "
+                                 f"{name} group's history_length or drop terms from it")
         torch.manual_seed(seed)
         self.env, self.device = env, obs["policy"].device
         self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std).to(self.device)

@@ -177,6 +177,33 @@ def parse_mirrors(mirrors):
     return tuple(x for x in ("lr", "fb") if x in m)
 
 
+def expand_history(table, term_dims, hist):
+    """A per-FRAME signed permutation `table` = (perm [n_sym, frame_dim], sign [n_sym, frame_dim]) -> the one of the term-major
+    history row of an env with observation history (`rl_env_set_obs_history`): term k of width `term_dims[k]` owns
+    max(hist[k], 1) frames side by side, oldest first, and a mirror acts on every frame slot alike - column j of slot s of term k takes
+    column perm[j] of slot s of the same term.  Raises if a copy moves a column out of its term's block (a history row keeps no place for it)."""
+    perm, sign = np.asarray(table[0]), np.asarray(table[1])
+    term_dims, hist = [int(d) for d in term_dims], [max(1, int(h)) for h in hist]
+    if len(term_dims) != len(hist):
+        raise ValueError(f"expand_history: {len(hist)} history lengths for {len(term_dims)} terms")
+    if perm.ndim != 2 or perm.shape != sign.shape or perm.shape[1] != sum(term_dims):
+        raise ValueError(f"expand_history: the table has shape {perm.shape}, the terms add up to {sum(term_dims)} columns")
+    out_p, out_s = [], []
+    foff = hoff = 0
+    for k, (d, H) in enumerate(zip(term_dims, hist)):
+        p = perm[:, foff:foff + d] - foff
+        if ((p < 0) | (p >= d)).any():
+            s, j = np.argwhere((p < 0) | (p >= d))[0]
+            raise ValueError(f"expand_history: copy {s} maps column {foff + j} (term {k}) to column {int(perm[s, foff + j])} outside the term's "
+                             f"block {foff}..{foff + d - 1}: a permutation that crosses term blocks has no history form")
+        for s in range(H):
+            out_p.append(hoff + s * d + p)
+            out_s.append(sign[:, foff:foff + d])
+        foff += d
+        hoff += H * d
+    return np.concatenate(out_p, axis=1).astype(np.int32), np.concatenate(out_s, axis=1).astype(np.float32)
+
+
 def tables_for_env(env_or_desc, mirrors=("lr",)) -> SymmetryTables:
     """`SymmetryTables` of a velocity task from its descriptor (`env.desc`): the joint names give the per-joint mirrors, the
     `task.policy` / `task.critic` term lists the layout of the two observation rows (the height scan's grid from
@@ -209,10 +236,14 @@ def tables_for_env(env_or_desc, mirrors=("lr",)) -> SymmetryTables:
         perm, sign = layout_tables(layout, names, scan=scan if "scan" in layout else None, **kw)
         return perm[rows], sign[rows]
 
-    def group(terms, n):
-        return table(tuple(KIND_BLOCK[OBS_KINDS[terms[i].kind]] for i in range(n)))
+    hist = getattr(env_or_desc, "obs_history", None) or {}  # an env with observation history: the same mirror in every frame slot
 
-    return SymmetryTables(obs=group(t.policy, t.n_policy), critic=group(t.critic, t.n_critic), act=table(ACTION_LAYOUT))
+    def group(terms, n, g):
+        tab = table(tuple(KIND_BLOCK[OBS_KINDS[terms[i].kind]] for i in range(n)))
+        lengths = hist.get(("policy", "critic")[g]) if isinstance(hist, dict) else None
+        return expand_history(tab, desc.obs_term_dims(g), lengths) if lengths else tab
+
+    return SymmetryTables(obs=group(t.policy, t.n_policy, 0), critic=group(t.critic, t.n_critic, 1), act=table(ACTION_LAYOUT))
 
 
 class SymmetryAugmentation:

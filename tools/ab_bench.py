@@ -70,7 +70,7 @@ def main():
     for l, v in res.items():
         if v:
             name = l.split(":", 1)[0] if (":" in l and "=" in l) else os.path.basename(l)
-            print(f"{name:28s} {a.task.split('Velocity-')[1]:28s} N={a.num_envs}{' steady' if a.steady else ''}: min {min(v):7.2f} us  median {sorted(v)[len(v)//2]:7.2f} us  ({len(v)} samples, {info.get(l, '')})")
+            print(f"{name:28s} {a.task.split('Velocity-')[1]:28s} N={a.num_envs}{' steady' if a.steady else ''}: min {min(v):7.2f} us  median {sorted(v)[len(v)//2]:7.2f} us  max {max(v):7.2f} us  ({len(v)} samples, {info.get(l, '')})")
 
 
 if __name__ == "__main__":

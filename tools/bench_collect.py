@@ -5,7 +5,8 @@
 then alg.compute_returns(obs) - every piece on the HIP kernels of this repo (actor + critic: rl_policy.hip, noise /
 log-prob / storage / GAE: rl_rollout.hip, env: rl_env.hip).  Random network weights: the arithmetic does not
 depend on them.
-    python tools/bench_collect.py [task] [num_envs] [iterations]"""
+    python tools/bench_collect.py [task] [num_envs] [iterations] [--obs-history N]
+--obs-history N: policy-group observation history of N frames, measured against history off in alternating windows of this process."""
 import os
 import sys
 import time
@@ -18,38 +19,42 @@ from robot_lab_amd.env import ManagerBasedRLEnv  # noqa: E402
 from robot_lab_amd.policy import MlpPolicy  # noqa: E402
 from robot_lab_amd.rollout import RolloutStorage  # noqa: E402
 
+ap_hist = 0
+if "--obs-history" in sys.argv:  # --obs-history N: policy-group observation history (rl_env_set_obs_history); runs history off / on alternating in this process
+    i = sys.argv.index("--obs-history")
+    ap_hist = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 task = sys.argv[1] if len(sys.argv) > 1 else "RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0"
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 ITERS = int(sys.argv[3]) if len(sys.argv) > 3 else 40
 T, GAMMA, LAM = 24, 0.99, 0.95  # rsl_rl_ppo_cfg.py:11,33-34
 FUSED = os.environ.get("RL_FUSED_RECORD", "1") == "1"
 PAIR = os.environ.get("RL_PAIR", "1") == "1"  # actor + critic in one launch (rl_mlp_forward_pair)
-env = ManagerBasedRLEnv(task, num_envs=N, seed=42, device="cuda:0")
-obs, _ = env.reset()
-od, cd, A = obs["policy"].shape[1], obs["critic"].shape[1], env.num_actions
-rng = np.random.default_rng(0)
-
-
-def net(dims):
-    ws = [(rng.standard_normal((dims[i + 1], dims[i])) / np.sqrt(dims[i])).astype(np.float32) for i in range(len(dims) - 1)]
-    return MlpPolicy(ws, [np.zeros(d, dtype=np.float32) for d in dims[1:]], "elu", device="cuda:0")
-
-
-actor, critic = net([od, 512, 256, 128, A]), net([cd, 512, 256, 128, 1])
-std = torch.ones(A, device="cuda:0")  # init_noise_std = 1.0 (rsl_rl_ppo_cfg.py:16)
-storage = RolloutStorage(N, T, od, cd, A, seed=1, device="cuda:0")
-
-
 GRAPH = os.environ.get("RL_GRAPH", "1") == "1"  # the whole iteration as one hipGraph launch (robot_lab_amd/collect.py)
 SMALL = os.environ.get("RL_CRITIC_SMALL", "1") == "1"  # (overlap) the critic through rl_mlp_forward_small
 FUSED_ACT = os.environ.get("RL_FUSED_ACT", "1") == "1"  # sampling / log-prob / the slot's first half in the actor + critic launch's epilogue (0: the act kernel)
 OVERLAP = os.environ.get("RL_OVERLAP", "0") == "1"  # the critic of step t on a second stream under env step t (0: actor + critic as one launch in front of act)
-if GRAPH and FUSED and PAIR:
-    from robot_lab_amd.collect import Collector  # noqa: E402
 
-    col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, overlap=OVERLAP, critic_small=SMALL, fused_act=FUSED_ACT)
-    iteration = lambda obs: col.collect()  # noqa: E731
-else:
+
+def setup(hist):
+    """-> (env, storage, iteration(obs) -> obs) of one collection loop; `hist`: policy-group history length (0: none)"""
+    env = ManagerBasedRLEnv(task, num_envs=N, seed=42, device="cuda:0", obs_history={"policy": hist} if hist else None)
+    obs, _ = env.reset()
+    od, cd, A = obs["policy"].shape[1], obs["critic"].shape[1], env.num_actions
+    rng = np.random.default_rng(0)
+
+    def net(dims):
+        ws = [(rng.standard_normal((dims[i + 1], dims[i])) / np.sqrt(dims[i])).astype(np.float32) for i in range(len(dims) - 1)]
+        return MlpPolicy(ws, [np.zeros(d, dtype=np.float32) for d in dims[1:]], "elu", device="cuda:0")
+
+    actor, critic = net([od, 512, 256, 128, A]), net([cd, 512, 256, 128, 1])
+    std = torch.ones(A, device="cuda:0")  # init_noise_std = 1.0 (rsl_rl_ppo_cfg.py:16)
+    storage = RolloutStorage(N, T, od, cd, A, seed=1, device="cuda:0")
+    if GRAPH and FUSED and PAIR:
+        from robot_lab_amd.collect import Collector  # noqa: E402
+
+        col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, overlap=OVERLAP, critic_small=SMALL, fused_act=FUSED_ACT)
+        return env, storage, (lambda obs: col.collect()), (actor, critic, col)
 
     def iteration(obs):
         storage.clear()
@@ -64,16 +69,60 @@ else:
         storage.compute_returns(critic(obs["critic"]), GAMMA, LAM)
         return obs
 
+    return env, storage, iteration, (actor, critic)
 
+
+def window(iteration, obs, iters):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        obs = iteration(obs)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, obs
+
+
+if ap_hist > 0:
+    # history off and on, alternating steady-state windows in ONE process: us per step of the collection loop and of a bare env.step()
+    # loop (zero actions), every window listed with the spread of each side
+    ROUNDS, STEPS = 6, 4000  # a window of either loop is 0.2 - 0.6 s of device time
+    sides = {}
+    with torch.inference_mode():
+        for h in (0, ap_hist):
+            env, storage, iteration, keep = setup(h)
+            obs = env.get_observations()
+            for _ in range(3):
+                obs = iteration(obs)
+            zero = torch.zeros(N, env.num_actions, device="cuda:0")
+            sides[h] = dict(env=env, storage=storage, iteration=iteration, keep=keep, obs=obs, zero=zero, collect=[], step=[])
+        for r in range(ROUNDS):
+            for h in ((0, ap_hist) if r % 2 == 0 else (ap_hist, 0)):
+                sd = sides[h]
+                dt, sd["obs"] = window(sd["iteration"], sd["obs"], ITERS)
+                sd["collect"].append(1e6 * dt / ITERS / T)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(STEPS):
+                    sd["env"].step(sd["zero"])
+                torch.cuda.synchronize()
+                sd["step"].append(1e6 * (time.perf_counter() - t0) / STEPS)
+    for h, sd in sides.items():
+        for what in ("collect", "step"):
+            v = np.array(sd[what])
+            print(f"{task} N={N} obs_history={h} policy_dim={sd['obs']['policy'].shape[1]} {what:7s} us/step: windows {np.round(v, 2).tolist()} "
+                  f"median {np.median(v):.2f} min {v.min():.2f} max {v.max():.2f}")
+    for what in ("collect", "step"):
+        off, on = np.median(sides[0][what]), np.median(sides[ap_hist][what])
+        print(f"{task} N={N} {what}: history {ap_hist} costs {on - off:+.2f} us/step ({100 * (on - off) / off:+.1f} %) over history off (medians of {ROUNDS} alternating windows)")
+    ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values())
+    print(f"finite: {ok}")
+    sys.exit(0 if ok else 1)
+
+env, storage, iteration, _keep = setup(0)
+obs = env.get_observations()
 with torch.inference_mode():
     for _ in range(3):
         obs = iteration(obs)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(ITERS):
-        obs = iteration(obs)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt, obs = window(iteration, obs, ITERS)
 ok = bool(torch.isfinite(storage.advantages).all() and torch.isfinite(storage.returns).all())
 print(f"{task} N={N} graph={int(GRAPH and FUSED and PAIR)} overlap={int(OVERLAP and GRAPH and FUSED and PAIR)} critic_small={int(SMALL)}: collection of {T} steps + GAE {1e3 * dt / ITERS:.3f} ms / iteration = {N * T * ITERS / dt / 1e6:.1f} M env-steps/s "
       f"({1e6 * dt / ITERS / T:.1f} us / step; finite: {ok}; adv mean {float(storage.advantages.mean()):+.2e} std {float(storage.advantages.std()):.4f})")

@@ -37,12 +37,14 @@ def main():
     ap.add_argument("--symmetry", default=None, help="mirrors of the symmetry data augmentation inside the update: lr, fb or lr,fb (default: none)")
     ap.add_argument("--mirror-loss", type=float, default=None, metavar="C", help="coefficient of the mirror loss on the --symmetry tables (default: off)")
     ap.add_argument("--no-data-augmentation", action="store_true", help="with --mirror-loss: the PPO terms stay on the stored rows")
+    ap.add_argument("--obs-history", type=int, default=0, metavar="N", help="policy-group observation history of N frames (IsaacLab's ObservationGroupCfg.history_length)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--also-terminate-on", default="", help="DIAGNOSTIC, not the reference's cfg: regex of body names added to the illegal-contact termination")
     a = ap.parse_args()
     if not a.symmetry and (a.mirror_loss is not None or a.no_data_augmentation):
         ap.error("--mirror-loss / --no-data-augmentation need --symmetry")
+    hist = {"policy": a.obs_history} if a.obs_history else None
     if a.also_terminate_on:
         import re
 
@@ -54,9 +56,9 @@ def main():
             desc.task.illegal_body_mask |= 1 << i
         desc.task.term_illegal_contact = 1
         print(f"DIAGNOSTIC run: illegal-contact termination extended to {[desc.body_names[i] for i in hit]}")
-        env = ManagerBasedRLEnv(desc=desc, extra=extra, num_envs=a.num_envs, seed=a.seed, device="cuda:0")
+        env = ManagerBasedRLEnv(desc=desc, extra=extra, num_envs=a.num_envs, seed=a.seed, device="cuda:0", obs_history=hist)
     else:
-        env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=a.seed, device="cuda:0")
+        env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=a.seed, device="cuda:0", obs_history=hist)
     print(env, flush=True)  # (names the step kernel: specialised on the task, or the interpreter)
     mirror = dict(mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation) if a.symmetry else {}
     tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror)
@@ -99,7 +101,7 @@ def main():
                   f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
     wall = time.perf_counter() - t_start
     n_steps = a.iterations * st.num_transitions_per_env * a.num_envs
-    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
+    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
                    collect_ms_per_iteration=1e3 * t_collect / a.iterations, update_ms_per_iteration=1e3 * t_update / a.iterations,
                    first=log[0], last=log[-1])
     print(json.dumps({k: v for k, v in summary.items() if k not in ("first", "last")}))
