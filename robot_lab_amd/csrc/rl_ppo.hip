@@ -46,6 +46,7 @@ constexpr int TK = 16;        // contraction slice
 constexpr int LD = TB + 4;    // LDS row stride: 4 r + i is a distinct bank for the 16 x 4 (r, i) pairs a wavefront stores at once
 constexpr int MAXP = 2 * RL_PPO_MAX_LAYERS + 1;
 constexpr float HALF_LOG_2PI = 0.9189385332046727f;
+constexpr int tiles_of(int x) { return (x + TB - 1) / TB; }  // output tiles along an edge of x entries
 
 enum { G_FWD = 0, G_DX = 1, G_DW = 2 };
 
@@ -258,6 +259,23 @@ __global__ __launch_bounds__(256) void ppo_reduce_kernel(RedBatch batch) {
   }
 }
 
+// ---- sh[q * NT] = sum over t of sh[q * NT + t] for the Q rows of NT doubles in LDS at `rows`: THE halving tree of this file (thread t < w adds entry
+// t + w to its own, w = NT / 2, NT / 4, .. 1), so every reduction adds in one order.  Called by all NT threads of the block after their writes to the rows.
+// (The LDS pointer and the do-while keep the instruction streams of the hand-written trees this replaced: profiles/ppo_hip_refactor_isa_identity.txt.)
+template <int NT, int Q>
+__device__ __forceinline__ void block_sum(double* rows) {
+  auto* sh = (__attribute__((address_space(3))) double*)rows;
+  __syncthreads();
+  for (int w = NT / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      int q = 0;
+      do sh[q * NT + threadIdx.x] += sh[q * NT + threadIdx.x + w];
+      while (++q < Q);
+    }
+    __syncthreads();
+  }
+}
+
 // ---- loss head
 struct DevState {
   double lr;           // the learning-rate word
@@ -354,23 +372,27 @@ __global__ __launch_bounds__(256) void ppo_head_kernel(HeadArgs a) {
     }
   }
   sh[0][threadIdx.x] = s_sur; sh[1][threadIdx.x] = s_val; sh[2][threadIdx.x] = s_kl;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-      for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + w];
-    __syncthreads();
-  }
+  block_sum<256, 3>(sh[0]);
   if (threadIdx.x < 3) a.partials[(size_t)blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
   if (MIRROR) {  // the fourth partial, through the same tree
     __syncthreads();
     sh[0][threadIdx.x] = s_mir;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) sh[0][threadIdx.x] += sh[0][threadIdx.x + w];
-      __syncthreads();
-    }
+    block_sum<256, 1>(sh[0]);
     if (threadIdx.x == 0) a.mirror_partials[blockIdx.x] = sh[0][0];
   }
+}
+
+// the KL-adaptive schedule and the counters of one mini-batch, by ONE thread (of ppo_head_finish_kernel<false>: the fused update; of
+// ppo_world_apply_kernel: the split one): the learning-rate word moves on the statistic `kl`, which is booked; the Adam step and the mini-batch are counted
+__device__ __forceinline__ void schedule_step(DevState* st, int adaptive, double desired_kl, float kl) {
+  if (adaptive) {  // (rl_ppo_create: adaptive implies desired_kl > 0)
+    // the host learner compares an fp32 statistic with thresholds formed in fp64
+    if (kl > (float)(2.0 * desired_kl)) st->lr = fmax(1e-5, st->lr / 1.5);
+    else if (kl > 0.f && kl < (float)(desired_kl / 2.0)) st->lr = fmin(1e-2, st->lr * 1.5);
+    st->acc[3] += (double)kl;
+  }
+  st->step += 1;
+  st->n_minibatches += 1;
 }
 
 // one workgroup of 64: orders the head's partial sums; with `apply` it books the statistics, moves the learning rate and counts the step.
@@ -387,12 +409,7 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* parti
     for (int b = threadIdx.x; b < nblocks; b += 64) s += partials[(size_t)b * 3 + q];
     sh[q][threadIdx.x] = s;
   }
-  __syncthreads();
-  for (int w = 32; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-      for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + w];
-    __syncthreads();
-  }
+  block_sum<64, 3>(sh[0]);
   if (threadIdx.x != 0 || !apply) return;
   float ent = 0.f;
   for (int k = 0; k < A; ++k) ent += 0.5f + HALF_LOG_2PI + logf(std[k]);
@@ -404,14 +421,7 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const double* parti
     *kl_word = adaptive ? kl : 0.f;
     return;
   }
-  if (adaptive) {  // (rl_ppo_create: adaptive implies desired_kl > 0)
-    // the host learner compares an fp32 statistic with thresholds formed in fp64
-    if (kl > (float)(2.0 * desired_kl)) st->lr = fmax(1e-5, st->lr / 1.5);
-    else if (kl > 0.f && kl < (float)(desired_kl / 2.0)) st->lr = fmin(1e-2, st->lr * 1.5);
-    st->acc[3] += (double)kl;
-  }
-  st->step += 1;
-  st->n_minibatches += 1;
+  schedule_step(st, adaptive, desired_kl, kl);
 }
 
 // the mirror loss's statistic: orders the fourth partials and books L_mirror = sum / count (count = (n_sym - 1) n0 A)
@@ -420,26 +430,15 @@ __global__ __launch_bounds__(64) void ppo_mirror_finish_kernel(const double* par
   double s = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 64) s += partials[b];
   sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 32; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
+  block_sum<64, 1>(sh);
   if (threadIdx.x == 0 && apply) st->mirror_acc += (double)(float)(sh[0] / count);
 }
 
 // what ppo_head_finish_kernel does under APPLY_FUSED past the local statistics, on the all-reduced wire word: the KL statistic is the ranks'
-// SUM / world in fp32 (dist.py `LearnerGroup.mean`), the learning-rate decision uses the same expressions
+// SUM / world in fp32 (dist.py `LearnerGroup.mean`), the rule is schedule_step
 __global__ __launch_bounds__(64) void ppo_world_apply_kernel(const float* kl_word, float world, DevState* st, int adaptive, double desired_kl) {
   if (threadIdx.x != 0) return;
-  if (adaptive) {
-    const float kl = *kl_word / world;
-    if (kl > (float)(2.0 * desired_kl)) st->lr = fmax(1e-5, st->lr / 1.5);
-    else if (kl > 0.f && kl < (float)(desired_kl / 2.0)) st->lr = fmin(1e-2, st->lr * 1.5);
-    st->acc[3] += (double)kl;
-  }
-  st->step += 1;
-  st->n_minibatches += 1;
+  schedule_step(st, adaptive, desired_kl, adaptive ? *kl_word / world : 0.f);
 }
 
 __global__ void ppo_set_optimizer_kernel(DevState* st, double lr, long long step) {
@@ -451,20 +450,20 @@ __global__ void ppo_set_optimizer_kernel(DevState* st, double lr, long long step
 // division in fp32 as `flat /= world_size` of the torch learner; SCALED = false never reads `world`
 constexpr int NORM_BLOCKS = 256;
 template <bool SCALED>
+__device__ __forceinline__ float grad_read(const float* g, long i, float world) {
+  return SCALED ? g[i] / world : g[i];
+}
+template <bool SCALED>
 __global__ __launch_bounds__(256) void ppo_sumsq_kernel(const float* g, long n, double* partial, float world) {
   __shared__ double sh[256];
   const long per = (n + NORM_BLOCKS - 1) / NORM_BLOCKS, b0 = (long)blockIdx.x * per, b1 = b0 + per < n ? b0 + per : n;
   double s = 0.0;
   for (long i = b0 + threadIdx.x; i < b1; i += 256) {
-    const float gi = SCALED ? g[i] / world : g[i];
+    const float gi = grad_read<SCALED>(g, i, world);
     s += (double)gi * (double)gi;
   }
   sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
+  block_sum<256, 1>(sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
 }
 
@@ -474,11 +473,7 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g,
                                                       float max_norm, float world) {
   __shared__ double sh[256];
   sh[threadIdx.x] = partial[threadIdx.x];  // NORM_BLOCKS == blockDim.x; every block adds the same numbers in the same order
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
+  block_sum<256, 1>(sh);
   const float norm = (float)sqrt(sh[0]);
   const float coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
   if (blockIdx.x == 0 && threadIdx.x == 0) st->grad_norm = (double)norm;
@@ -487,7 +482,7 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g,
   const double step = (double)st->step;
   const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
   const float step_size = (float)(st->lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  const float gi = (SCALED ? g[i] / world : g[i]) * coef;
+  const float gi = grad_read<SCALED>(g, i, world) * coef;
   const float m = m1[i] + 0.1f * (gi - m1[i]);                       // exp_avg.lerp_(grad, 1 - beta1)
   const float v = m2[i] * 0.999f + (float)(1.0 - 0.999) * gi * gi;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
   m1[i] = m;
@@ -572,7 +567,7 @@ bool alloc_rows(rl_ppo* p, size_t rows) {
     for (int l = 0; l < p->L && ok; ++l) {
       const int Nn = N.dims[l + 1], K = N.dims[l];
       ok = dalloc(own, &N.h[l + 1], rows_k * Nn) && dalloc(own, &N.dz[l + 1], rows_k * Nn);
-      const int tiles = ((Nn + TB - 1) / TB) * ((K + TB - 1) / TB);
+      const int tiles = tiles_of(Nn) * tiles_of(K);
       N.S[l] = std::max(1, std::min(128 / tiles, s_cap));  // ~128 workgroups per layer and network: 1024 in the one dW launch of the A1 networks
       ok = ok && dalloc(own, &N.part[l], (size_t)N.S[l] * ((size_t)Nn * K + Nn));
     }
@@ -597,19 +592,45 @@ int chunk_rows(int n, int S) {  // rows per chunk: a multiple of the GEMM's slic
   return std::max(TK, (c + TK - 1) / TK * TK);
 }
 
+// the launch dispatcher: a runtime flag names the template side of a kernel, the launch that follows has ONE argument list
+template <class K>
+K* side(bool flag, K* on, K* off) {
+  return flag ? on : off;
+}
+
 // sum of squares -> clip -> Adam -> floor of std on the flat gradient; with a world > 1 on g[i] / world (the wire holds the ranks' SUM)
 void optimiser_step(rl_ppo* p, hipStream_t s) {
   const float world = (float)std::max(p->world, 1);
-  const dim3 adam_grid((unsigned)((p->n_params + 255) / 256));
-  if (p->world > 1) {
-    hipLaunchKernelGGL(ppo_sumsq_kernel<true>, dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part, world);
-    hipLaunchKernelGGL(ppo_adam_kernel<true>, adam_grid, dim3(256), 0, s, p->params, p->grads, p->m1, p->m2, p->n_params, p->A, p->norm_part, p->st,
-                       p->hp.max_grad_norm, world);
+  const bool scaled = p->world > 1;
+  hipLaunchKernelGGL(side(scaled, ppo_sumsq_kernel<true>, ppo_sumsq_kernel<false>), dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part,
+                     world);
+  hipLaunchKernelGGL(side(scaled, ppo_adam_kernel<true>, ppo_adam_kernel<false>), dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, s, p->params,
+                     p->grads, p->m1, p->m2, p->n_params, p->A, p->norm_part, p->st, p->hp.max_grad_norm, world);
+}
+
+// fills (a zeroed) `g` with the problem of `mode` for layer l of network k over `rows` rows (see GemmProb): the operands of either network, the
+// gather through the n0 indices at `idx` and the symmetry tables where the layer's input is the stored batch, the tile grid
+void gemm_prob(GemmProb& g, const rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int mode, int k, int l, int rows) {
+  const Net& N = p->net[k];
+  const int K = N.dims[l], Nn = N.dims[l + 1];
+  const float* x = l > 0 ? N.h[l] : k == 0 ? b->observations : b->privileged_observations;  // the layer's input [rows][K]
+  const float* W = p->params + N.w_off[l];     // [Nn][K]
+  if (mode == G_FWD) {
+    g.A = x; g.lda = K; g.B = W; g.ldb = K; g.aux = p->params + N.b_off[l]; g.C = N.h[l + 1]; g.ldc = Nn;
+    g.I = rows; g.J = Nn; g.R = K; g.act = l + 1 < p->L;
+  } else if (mode == G_DX) {
+    g.A = N.dz[l + 1]; g.lda = Nn; g.B = W; g.ldb = K; g.aux = N.h[l]; g.ldaux = K; g.C = N.dz[l]; g.ldc = K;
+    g.I = rows; g.J = K; g.R = Nn;
   } else {
-    hipLaunchKernelGGL(ppo_sumsq_kernel<false>, dim3(NORM_BLOCKS), dim3(256), 0, s, p->grads, p->n_params, p->norm_part, world);
-    hipLaunchKernelGGL(ppo_adam_kernel<false>, adam_grid, dim3(256), 0, s, p->params, p->grads, p->m1, p->m2, p->n_params, p->A, p->norm_part, p->st,
-                       p->hp.max_grad_norm, world);
+    g.A = N.dz[l + 1]; g.lda = Nn; g.B = x; g.ldb = K; g.C = N.part[l]; g.ldc = K;
+    g.I = Nn; g.J = K; g.R = rows;
+    g.S = N.S[l]; g.chunk = chunk_rows(rows, g.S); g.cstride = (long)Nn * K + Nn;
   }
+  if (mode != G_DX && l == 0) {
+    g.gidx = idx;
+    if (p->n_sym > 0) { g.sym = p->sym[k]; g.n0 = n0; }
+  }
+  g.tilesJ = tiles_of(g.J); g.ntiles = tiles_of(g.I) * g.tilesJ;
 }
 
 // the launches of one mini-batch (see the head of this file); `apply`: APPLY_NONE (the gradient alone), APPLY_FUSED (statistics, learning rate
@@ -624,25 +645,14 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
   if (!p->rows_ready && !alloc_rows(p, (size_t)(sym ? p->n_sym : 1) * (size_t)p->max_rows))
     return fail("device allocation of the mini-batch buffers failed");  // nothing is launched; a later call tries again
   p->started = true;
-  const float* X[2] = {b->observations, b->privileged_observations};
   for (int l = 0; l < L; ++l) {
     GemmBatch gb{};
     int tiles = 0;
     for (int k = 0; k < 2; ++k) {
-      const Net& N = p->net[k];
-      GemmProb& g = gb.p[k];
-      g.A = l == 0 ? X[k] : N.h[l]; g.gidx = l == 0 ? idx : nullptr; g.lda = N.dims[l];
-      g.B = p->params + N.w_off[l]; g.ldb = N.dims[l];
-      g.aux = p->params + N.b_off[l];
-      g.C = N.h[l + 1]; g.ldc = N.dims[l + 1];
-      g.I = rows_of[k]; g.J = N.dims[l + 1]; g.R = N.dims[l];
-      g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
-      g.act = l + 1 < L;
-      if (sym && l == 0) { g.sym = p->sym[k]; g.n0 = n0; }
-      tiles = std::max(tiles, g.ntiles);
+      gemm_prob(gb.p[k], p, b, idx, n0, G_FWD, k, l, rows_of[k]);
+      tiles = std::max(tiles, gb.p[k].ntiles);
     }
-    if (sym && l == 0) hipLaunchKernelGGL((ppo_gemm_kernel<G_FWD, true>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
-    else hipLaunchKernelGGL((ppo_gemm_kernel<G_FWD, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+    hipLaunchKernelGGL(side(sym && l == 0, ppo_gemm_kernel<G_FWD, true>, ppo_gemm_kernel<G_FWD, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
   }
   {
     HeadArgs a{};
@@ -653,16 +663,11 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
     a.asym = p->sym[2]; a.n0 = n0;
     a.n_terms = n_terms; a.mirror_coeff = p->mirror; a.mirror_partials = p->mirror_part;
     const int blocks = (n + 255) / 256;
-    if (mirror) hipLaunchKernelGGL((ppo_head_kernel<true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (sym) hipLaunchKernelGGL(ppo_head_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(ppo_head_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(side(mirror, ppo_head_kernel<true, true>, side(sym, ppo_head_kernel<true>, ppo_head_kernel<false>)), dim3(blocks), dim3(256), 0, s, a);
     const int adaptive = p->hp.schedule == RL_PPO_SCHEDULE_ADAPTIVE ? 1 : 0;
-    if (apply == APPLY_LOCAL)
-      hipLaunchKernelGGL(ppo_head_finish_kernel<true>, dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0, p->params, p->A, p->st, 1, adaptive,
-                         p->hp.desired_kl, p->grads + p->n_params);
-    else
-      hipLaunchKernelGGL(ppo_head_finish_kernel<false>, dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0, p->params, p->A, p->st, apply ? 1 : 0,
-                         adaptive, p->hp.desired_kl, (float*)nullptr);
+    const bool local = apply == APPLY_LOCAL;  // the KL word goes to the wire, behind the gradient
+    hipLaunchKernelGGL(side(local, ppo_head_finish_kernel<true>, ppo_head_finish_kernel<false>), dim3(1), dim3(64), 0, s, p->head_part, blocks, n_terms, n0,
+                       p->params, p->A, p->st, apply ? 1 : 0, adaptive, p->hp.desired_kl, local ? p->grads + p->n_params : (float*)nullptr);
     if (mirror)
       hipLaunchKernelGGL(ppo_mirror_finish_kernel, dim3(1), dim3(64), 0, s, p->mirror_part, blocks, (double)(p->n_sym - 1) * (double)n0 * (double)p->A, p->st,
                          apply ? 1 : 0);
@@ -671,15 +676,8 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
     GemmBatch gb{};
     int tiles = 0;
     for (int k = 0; k < 2; ++k) {
-      const Net& N = p->net[k];
-      GemmProb& g = gb.p[k];
-      g.A = N.dz[l + 1]; g.lda = N.dims[l + 1];
-      g.B = p->params + N.w_off[l]; g.ldb = N.dims[l];
-      g.aux = N.h[l]; g.ldaux = N.dims[l];
-      g.C = N.dz[l]; g.ldc = N.dims[l];
-      g.I = rows_of[k]; g.J = N.dims[l]; g.R = N.dims[l + 1];
-      g.tilesJ = (g.J + TB - 1) / TB; g.ntiles = ((g.I + TB - 1) / TB) * g.tilesJ;
-      tiles = std::max(tiles, g.ntiles);
+      gemm_prob(gb.p[k], p, b, idx, n0, G_DX, k, l, rows_of[k]);
+      tiles = std::max(tiles, gb.p[k].ntiles);
     }
     hipLaunchKernelGGL((ppo_gemm_kernel<G_DX, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
   }
@@ -694,13 +692,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
         const Net& N = p->net[k];
         const int Nn = N.dims[l + 1], K = N.dims[l];
         GemmProb& g = gb.p[np];
-        g.A = N.dz[l + 1]; g.lda = Nn;
-        g.B = l == 0 ? X[k] : N.h[l]; g.gidx = l == 0 ? idx : nullptr; g.ldb = K;
-        g.C = N.part[l]; g.ldc = K;
-        g.I = Nn; g.J = K; g.R = rows_of[k];
-        g.tilesJ = (K + TB - 1) / TB; g.ntiles = ((Nn + TB - 1) / TB) * g.tilesJ;
-        g.S = N.S[l]; g.chunk = chunk_rows(g.R, g.S); g.cstride = (long)Nn * K + Nn;
-        if (sym && l == 0) { g.sym = p->sym[k]; g.n0 = n0; }
+        gemm_prob(g, p, b, idx, n0, G_DW, k, l, rows_of[k]);
         ColProb& c = cb.p[np];
         c.Z = N.dz[l + 1]; c.part = N.part[l]; c.N = Nn; c.M = g.R; c.ld = Nn; c.S = g.S; c.chunk = g.chunk; c.stride = g.cstride; c.off = (long)Nn * K;
         RedProb& r = rb.p[np];
@@ -712,8 +704,7 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
     RedProb& r = rb.p[np];
     r.part = p->std_part; r.out = p->grads; r.count = p->A; r.stride = p->A; r.S = p->S_std;
     colx = std::max(colx, (p->A + 63) / 64); Smax = std::max(Smax, p->S_std);
-    if (sym) hipLaunchKernelGGL((ppo_gemm_kernel<G_DW, true>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
-    else hipLaunchKernelGGL((ppo_gemm_kernel<G_DW, false>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
+    hipLaunchKernelGGL(side(sym, ppo_gemm_kernel<G_DW, true>, ppo_gemm_kernel<G_DW, false>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
     hipLaunchKernelGGL(ppo_colsum_kernel, dim3(colx, Smax, np + 1), dim3(256), 0, s, cb);
     hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)std::min<long>((redmax + 255) / 256, 512), np + 1), dim3(256), 0, s, rb);
   }
@@ -721,10 +712,24 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
   return check_launch();
 }
 
-int check_batch(const rl_ppo_batch* b) {
+// the guard of the entry points that enqueue mini-batches: arguments, the batch's pointers, `rows` (named `what` in the refusal) per mini-batch, the
+// device; last and only with `pending`: that refusal while an rl_ppo_minibatch_local waits for its rl_ppo_minibatch_apply
+int enter(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int rows, const char* what, const char* pending) {
+  if (!p || !idx) return fail("null argument");
   if (!b || !b->observations || !b->privileged_observations || !b->actions || !b->values || !b->returns || !b->advantages || !b->actions_log_prob ||
       !b->mu || !b->sigma)
     return fail("null batch pointer");
+  if (rows < 1 || rows > p->max_rows) return fail(std::string(what) + " outside 1..max_rows_per_minibatch");
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (pending && p->local_pending) return fail(pending);
+  return 0;
+}
+
+// waits for the stream and copies the state block to the host
+int read_state(rl_ppo* p, void* stream, DevState* st, const char* what) {
+  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("stream synchronisation failed");
+  if (hipMemcpy(st, p->st, sizeof(*st), hipMemcpyDeviceToHost) != hipSuccess) return fail(std::string(what) + " copy failed");
   return 0;
 }
 
@@ -921,21 +926,14 @@ int rl_ppo_get_flat(rl_ppo* p, int32_t which, float* dst_dev, void* stream) {
 }
 
 int rl_ppo_minibatch_grad(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream) {
-  if (!p || !idx_dev) return fail("null argument");
-  if (check_batch(batch)) return -1;
-  if (n_idx < 1 || n_idx > p->max_rows) return fail("n_idx outside 1..max_rows_per_minibatch");
-  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (enter(p, batch, idx_dev, n_idx, "n_idx", nullptr)) return -1;
   return minibatch(p, batch, idx_dev, n_idx, APPLY_NONE, (hipStream_t)stream);
 }
 
 int rl_ppo_update(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* perm_dev, int32_t n_rows, void* stream) {
-  if (!p || !perm_dev) return fail("null argument");
-  if (check_batch(batch)) return -1;
-  const int mb = n_rows / p->hp.num_mini_batches;
-  if (mb < 1 || mb > p->max_rows) return fail("rows per mini-batch outside 1..max_rows_per_minibatch");
-  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  const int mb = p ? n_rows / p->hp.num_mini_batches : 0;
+  if (enter(p, batch, perm_dev, mb, "rows per mini-batch", "rl_ppo_update: an rl_ppo_minibatch_local waits for its rl_ppo_minibatch_apply")) return -1;
   hipStream_t s = (hipStream_t)stream;
-  if (p->local_pending) return fail("rl_ppo_update: an rl_ppo_minibatch_local waits for its rl_ppo_minibatch_apply");
   if (reset_statistics(p, s)) return -1;
   for (int e = 0; e < p->hp.num_learning_epochs; ++e)
     for (int i = 0; i < p->hp.num_mini_batches; ++i)
@@ -967,11 +965,7 @@ int rl_ppo_update_begin(rl_ppo* p, void* stream) {
 }
 
 int rl_ppo_minibatch_local(rl_ppo* p, const rl_ppo_batch* batch, const int64_t* idx_dev, int32_t n_idx, void* stream) {
-  if (!p || !idx_dev) return fail("null argument");
-  if (check_batch(batch)) return -1;
-  if (n_idx < 1 || n_idx > p->max_rows) return fail("n_idx outside 1..max_rows_per_minibatch");
-  if (p->local_pending) return fail("rl_ppo_minibatch_local: the previous mini-batch waits for its rl_ppo_minibatch_apply");
-  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (enter(p, batch, idx_dev, n_idx, "n_idx", "rl_ppo_minibatch_local: the previous mini-batch waits for its rl_ppo_minibatch_apply")) return -1;
   if (minibatch(p, batch, idx_dev, n_idx, APPLY_LOCAL, (hipStream_t)stream)) return -1;
   p->local_pending = true;
   return 0;
@@ -999,10 +993,8 @@ int rl_ppo_set_flat(rl_ppo* p, int32_t which, const float* src_dev, void* stream
 
 int rl_ppo_get_optimizer(rl_ppo* p, double* lr, int64_t* step, void* stream) {
   if (!p || !lr || !step) return fail("null argument");
-  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("stream synchronisation failed");
   DevState st{};
-  if (hipMemcpy(&st, p->st, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return fail("optimiser state copy failed");
+  if (read_state(p, stream, &st, "optimiser state")) return -1;
   *lr = st.lr;
   *step = (int64_t)st.step;
   return 0;
@@ -1019,10 +1011,8 @@ int rl_ppo_set_optimizer(rl_ppo* p, double lr, int64_t step, void* stream) {
 
 namespace {
 int read_stats(rl_ppo* p, double* out, int n_out, void* stream) {
-  if (hipSetDevice(p->device) != hipSuccess) return fail("hipSetDevice failed");
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("stream synchronisation failed");
   DevState st{};
-  if (hipMemcpy(&st, p->st, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return fail("statistics copy failed");
+  if (read_state(p, stream, &st, "statistics")) return -1;
   const double n = st.n_minibatches > 0 ? (double)st.n_minibatches : 1.0;
   out[0] = st.acc[0] / n; out[1] = st.acc[1] / n; out[2] = st.acc[2] / n; out[3] = st.acc[3] / n;
   out[4] = st.lr; out[5] = st.grad_norm; out[6] = (double)st.n_minibatches; out[7] = (double)st.step;

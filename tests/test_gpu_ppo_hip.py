@@ -8,56 +8,22 @@ expressions that differ in summation order only (an MFMA chain accumulates linea
 tree-reduce), so a small multiple - 8 - of the fp32 learner's own distance from fp64 is legitimate; a missing term, a wrong ELU' mask
 or bf16 products are 100 x or more.
 
-Fixed synthetic inputs (no env): ActorCritic(45, 235, 12) under torch.manual_seed(0); a storage built like `_fake_storage` of
-tests/test_ppo.py with T = 24, N = 256 (6144 rows, mini-batches of 1536); then every parameter perturbed by 0.01 randn mean|p| so that
+Fixed synthetic inputs (no env): ActorCritic(45, 235, 12) under torch.manual_seed(0); a storage built by `fake_storage` of
+tests/ppo_helpers.py with T = 24, N = 256 (6144 rows, mini-batches of 1536); then every parameter perturbed by 0.01 randn mean|p| so that
 the probability ratio is not 1."""
 import copy
-import types
+import functools
 
 import numpy as np
 import pytest
+
+from ppo_helpers import DEV, cast as _cast, fake_storage as _fake_storage, gen as _gen, perm as perm_of, split as _split, torch_learner as _torch_learner
 
 pytestmark = pytest.mark.gpu
 
 T, N, OD, CD, A = 24, 256, 45, 235, 12
 B, MB = T * N, T * N // 4
-DEV = "cuda:0"
-
-
-def _fake_storage(policy, T, N, od, cd, A, seed=0):
-    """`_fake_storage` of tests/test_ppo.py (action dimension 0 being positive is "good")"""
-    import torch
-
-    from robot_lab_amd.ppo import gaussian_log_prob
-
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, od, generator=g), torch.randn(T, N, cd, generator=g)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
-
-
-def _cast(st, dtype, rows=None):
-    """the storage on the device in `dtype`; `rows`: only these rows of the flat batch, as a 1 x len(rows) storage"""
-    import torch
-
-    out = types.SimpleNamespace(num_transitions_per_env=st.num_transitions_per_env, num_envs=st.num_envs)
-    for k, v in vars(st).items():
-        if torch.is_tensor(v):
-            v = v.to(device=DEV, dtype=dtype)
-            if rows is not None:
-                v = v.reshape(B, -1)[rows].unsqueeze(0).contiguous()
-            setattr(out, k, v)
-    if rows is not None:
-        out.num_transitions_per_env, out.num_envs = 1, len(rows)
-    return out
+_perm = functools.partial(perm_of, B)
 
 
 @pytest.fixture(scope="module")
@@ -74,45 +40,6 @@ def case():
         for p in pol.parameters():
             p.add_(0.01 * torch.randn(p.shape, generator=g) * p.abs().mean())
     return pol, st
-
-
-def _gen(seed=1):
-    import torch
-
-    return torch.Generator(device=DEV).manual_seed(seed)
-
-
-def _perm(seed=1):
-    """the permutation PPO.update draws from `_gen(seed)`"""
-    import torch
-
-    return torch.randperm(B, device=DEV, generator=_gen(seed))
-
-
-def _torch_learner(pol, dtype, **kw):
-    """the unchanged torch learner on a copy of `pol`; records the learning rate in force at every optimiser step"""
-    from robot_lab_amd.ppo import PPO
-
-    p = copy.deepcopy(pol).to(device=DEV, dtype=dtype)
-    alg = PPO(p, **kw)
-    alg.lr_path = []
-    step = alg.optimizer.step
-
-    def recording_step(*a, **k):
-        alg.lr_path.append(alg.optimizer.param_groups[0]["lr"])
-        return step(*a, **k)
-
-    alg.optimizer.step = recording_step
-    return alg
-
-
-def _split(flat, pol):
-    out, o = {}, 0
-    for name, p in pol.named_parameters():
-        out[name] = flat[o:o + p.numel()].double().cpu()
-        o += p.numel()
-    assert o == flat.numel()
-    return out
 
 
 @pytest.mark.parametrize("rows", [MB, 1000])

@@ -1,7 +1,7 @@
 """`-m gpu`: rsl_rl's mirror loss inside the HIP PPO learner (`rl_ppo_set_mirror_loss`, the MIRROR instantiation of the loss head in
 csrc/rl_ppo.hip, `ppo_hip.HipPPO(symmetry=..., mirror_loss=..., data_augmentation=...)`) against the torch learner of robot_lab_amd/ppo.py.
 
-Setup and bounds are those of tests/test_gpu_ppo_hip_symmetry.py (its helpers are restated here): ActorCritic(45, 235, 12), a `_fake_storage`
+Setup and bounds are those of tests/test_gpu_ppo_hip_symmetry.py: ActorCritic(45, 235, 12), a `fake_storage`
 with T = 24, N = 256, parameters perturbed, random signed-permutation tables from `default_rng(11)`, coefficient 0.5.  The comparator is
 `ppo.PPO(symmetry=..., mirror_loss=..., data_augmentation=...)` in fp64 - its rule is pinned to the formula by tests/test_ppo_mirror_loss.py -
 and the same in fp32 measures what fp32 round-off alone does (d); never the HIP learner itself.
@@ -10,73 +10,21 @@ max <= sum of the learning rates; statistics within 8 x the fp32 learner's own e
 Two modes: (a) with the data augmentation (every stage sees the n_sym n rows), (b) without (the critic, the std column sum and the loss means see the
 n stored rows, the actor n_sym n)."""
 import copy
-import types
+import functools
 
 import numpy as np
 import pytest
+
+from ppo_helpers import (DEV, cast as _cast, compare_gradients as _compare, fake_storage as _fake_storage, gen as _gen, perm as perm_of, split as _split, tables,
+                         torch_learner as _torch_learner)
 
 pytestmark = pytest.mark.gpu
 
 T, N, OD, CD, A = 24, 256, 45, 235, 12
 B, MB = T * N, T * N // 4
-DEV = "cuda:0"
+_perm, _tables = functools.partial(perm_of, B), functools.partial(tables, (OD, CD, A))
 PERTURB_SEED = 1  # with it the fp64 and the fp32 torch learner walk the same 20-step learning-rate path in both modes (asserted below)
 COEFF = 0.5
-
-
-def _fake_storage(policy, T, N, od, cd, A, seed=0):
-    """`_fake_storage` of tests/test_ppo.py (action dimension 0 being positive is "good")"""
-    import torch
-
-    from robot_lab_amd.ppo import gaussian_log_prob
-
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, od, generator=g), torch.randn(T, N, cd, generator=g)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
-
-
-def _cast(st, dtype):
-    import torch
-
-    out = types.SimpleNamespace(num_transitions_per_env=st.num_transitions_per_env, num_envs=st.num_envs)
-    for k, v in vars(st).items():
-        if torch.is_tensor(v):
-            setattr(out, k, v.to(device=DEV, dtype=dtype))
-    return out
-
-
-def _random_table(rng, n_sym, dim):
-    perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
-    sign = np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
-    return perm, sign
-
-
-def _tables(n_sym, critic=True, seed=11):
-    from robot_lab_amd.symmetry import SymmetryTables
-
-    rng = np.random.default_rng(seed)
-    obs, cri, act = _random_table(rng, n_sym, OD), _random_table(rng, n_sym, CD), _random_table(rng, n_sym, A)
-    return SymmetryTables(obs=obs, critic=cri if critic else None, act=act)
-
-
-def _rows(st, idx):
-    """the rows `idx` of a `_cast` storage as a 1 x len(idx) storage: one epoch of one mini-batch of the torch learner is then the gradient on them"""
-    import torch
-
-    out = types.SimpleNamespace(num_transitions_per_env=1, num_envs=len(idx))
-    for k, v in vars(st).items():
-        if torch.is_tensor(v):
-            setattr(out, k, v.reshape(B, -1)[idx].unsqueeze(0).contiguous())
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -97,44 +45,6 @@ def case():
     return pol, st, zero_adv
 
 
-def _gen(seed=1):
-    import torch
-
-    return torch.Generator(device=DEV).manual_seed(seed)
-
-
-def _perm(seed=1):
-    import torch
-
-    return torch.randperm(B, device=DEV, generator=_gen(seed))
-
-
-def _torch_learner(pol, dtype, **kw):
-    """the torch learner on a copy of `pol`; records the learning rate in force at every optimiser step"""
-    from robot_lab_amd.ppo import PPO
-
-    p = copy.deepcopy(pol).to(device=DEV, dtype=dtype)
-    alg = PPO(p, **kw)
-    alg.lr_path = []
-    step = alg.optimizer.step
-
-    def recording_step(*a, **k):
-        alg.lr_path.append(alg.optimizer.param_groups[0]["lr"])
-        return step(*a, **k)
-
-    alg.optimizer.step = recording_step
-    return alg
-
-
-def _split(flat, pol):
-    out, o = {}, 0
-    for name, p in pol.named_parameters():
-        out[name] = flat[o:o + p.numel()].double().cpu()
-        o += p.numel()
-    assert o == flat.numel()
-    return out
-
-
 _REFERENCES = {}
 
 
@@ -149,30 +59,10 @@ def _reference(pol, st, rows, n_sym, critic, augment, **kw):
         for dtype in (torch.float64, torch.float32):
             alg = _torch_learner(pol, dtype, num_learning_epochs=1, num_mini_batches=1, max_grad_norm=1e30, symmetry=tab, mirror_loss=COEFF,
                                  data_augmentation=augment, **kw)
-            alg.update(_rows(_cast(st, dtype), idx), _gen(5))
+            alg.update(_cast(st, dtype, rows=idx), _gen(5))
             ref[dtype] = {n: p.grad.detach().double().cpu() for n, p in alg.policy.named_parameters()}
         _REFERENCES[key] = ref
     return _REFERENCES[key]
-
-
-def _compare(title, g_hip, ref, only=None):
-    """prints the table, returns the tensors above e <= max(8 d, one fp32 spacing of max|g64| relative to it)"""
-    import torch
-
-    print(f"\n{title}\n{'tensor':<18}{'max|g64|':>12}{'e (hip)':>12}{'d (torch32)':>13}{'e/d':>8}{'floor':>12}")
-    bad = []
-    for n, g64 in ref[torch.float64].items():
-        if only is not None and not n.startswith(only):
-            continue
-        scale = g64.abs().max().item()
-        assert scale > 0, n
-        e = (g_hip[n].reshape(g64.shape) - g64).abs().max().item() / scale
-        d = (ref[torch.float32][n] - g64).abs().max().item() / scale
-        floor = float(np.spacing(np.float32(scale))) / scale
-        print(f"{n:<18}{scale:12.4e}{e:12.3e}{d:13.3e}{e / d if d else float('inf'):8.2f}{floor:12.3e}")
-        if not e <= max(8 * d, floor):
-            bad.append((n, e, d, floor))
-    return bad
 
 
 MODES = {"a": True, "b": False}  # data_augmentation

@@ -11,61 +11,20 @@ Bounds: those of tests/test_gpu_ppo_hip.py (e <= 8 d per tensor; q999 <= max(8 q
 `ulp` idea as a floor of the gradient bound: one fp32 spacing of the tensor's largest fp64 gradient entry, relative to that entry - below it
 an fp32 result cannot be told from the fp64 one, whatever d happens to be."""
 import copy
+import functools
 import types
 
 import numpy as np
 import pytest
 
+from ppo_helpers import DEV, cast as _cast, fake_storage as _fake_storage, gen as _gen, perm as perm_of, split as _split, tables, torch_learner as _torch_learner
+
 pytestmark = pytest.mark.gpu
 
 T, N, OD, CD, A = 24, 256, 45, 235, 12
 B, MB = T * N, T * N // 4
-DEV = "cuda:0"
+_perm, _tables = functools.partial(perm_of, B), functools.partial(tables, (OD, CD, A))
 PERTURB_SEED = 1  # with it the fp64 and the fp32 torch learner walk the same 20-step learning-rate path under TABLES(2) (asserted below)
-
-
-def _fake_storage(policy, T, N, od, cd, A, seed=0):
-    """`_fake_storage` of tests/test_ppo.py (action dimension 0 being positive is "good")"""
-    import torch
-
-    from robot_lab_amd.ppo import gaussian_log_prob
-
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, od, generator=g), torch.randn(T, N, cd, generator=g)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
-
-
-def _cast(st, dtype):
-    import torch
-
-    out = types.SimpleNamespace(num_transitions_per_env=st.num_transitions_per_env, num_envs=st.num_envs)
-    for k, v in vars(st).items():
-        if torch.is_tensor(v):
-            setattr(out, k, v.to(device=DEV, dtype=dtype))
-    return out
-
-
-def _random_table(rng, n_sym, dim):
-    perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
-    sign = np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
-    return perm, sign
-
-
-def _tables(n_sym, critic=True, seed=11):
-    from robot_lab_amd.symmetry import SymmetryTables
-
-    rng = np.random.default_rng(seed)
-    obs, cri, act = _random_table(rng, n_sym, OD), _random_table(rng, n_sym, CD), _random_table(rng, n_sym, A)
-    return SymmetryTables(obs=obs, critic=cri if critic else None, act=act)
 
 
 def _materialise(st, tab, idx):
@@ -106,44 +65,6 @@ def case():
         for p in pol.parameters():
             p.add_(0.01 * torch.randn(p.shape, generator=g) * p.abs().mean())
     return pol, st
-
-
-def _gen(seed=1):
-    import torch
-
-    return torch.Generator(device=DEV).manual_seed(seed)
-
-
-def _perm(seed=1):
-    import torch
-
-    return torch.randperm(B, device=DEV, generator=_gen(seed))
-
-
-def _torch_learner(pol, dtype, **kw):
-    """the torch learner on a copy of `pol`; records the learning rate in force at every optimiser step"""
-    from robot_lab_amd.ppo import PPO
-
-    p = copy.deepcopy(pol).to(device=DEV, dtype=dtype)
-    alg = PPO(p, **kw)
-    alg.lr_path = []
-    step = alg.optimizer.step
-
-    def recording_step(*a, **k):
-        alg.lr_path.append(alg.optimizer.param_groups[0]["lr"])
-        return step(*a, **k)
-
-    alg.optimizer.step = recording_step
-    return alg
-
-
-def _split(flat, pol):
-    out, o = {}, 0
-    for name, p in pol.named_parameters():
-        out[name] = flat[o:o + p.numel()].double().cpu()
-        o += p.numel()
-    assert o == flat.numel()
-    return out
 
 
 @pytest.mark.parametrize("rows,n_sym,critic", [(1000, 4, True), (37, 2, True), (MB, 2, False)], ids=["1000x4", "37x2", "1536x2-critic-replicated"])

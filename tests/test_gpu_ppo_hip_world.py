@@ -14,10 +14,11 @@ mini-batches of 37 (row tails of every tile, a partial 16-row slice, empty dW ch
 0.01 randn mean|p|.  The single learner's update is computed once (fixture `single`) and shared."""
 import copy
 import ctypes as C
-import types
 
 import numpy as np
 import pytest
+
+from ppo_helpers import DEV, cast as _cast, fake_storage as _fake_storage, gen as _gen
 
 pytestmark = pytest.mark.gpu
 
@@ -25,38 +26,7 @@ T, N, OD, CD, A = 4, 37, 19, 23, 5
 HID = (40, 24)
 B, NMB, EPOCHS = T * N, 4, 2
 MB = B // NMB
-DEV = "cuda:0"
 KW = dict(num_learning_epochs=EPOCHS, num_mini_batches=NMB)
-
-
-def _fake_storage(policy, T, N, od, cd, A, seed=0):
-    """`_fake_storage` of tests/test_gpu_ppo_hip.py (action dimension 0 being positive is "good")"""
-    import torch
-
-    from robot_lab_amd.ppo import gaussian_log_prob
-
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, od, generator=g), torch.randn(T, N, cd, generator=g)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
-
-
-def _cast(st, dtype):
-    import torch
-
-    out = types.SimpleNamespace(num_transitions_per_env=st.num_transitions_per_env, num_envs=st.num_envs)
-    for k, v in vars(st).items():
-        if torch.is_tensor(v):
-            setattr(out, k, v.to(device=DEV, dtype=dtype))
-    return out
 
 
 class _Ranks:
@@ -109,12 +79,6 @@ def case():
         for p in pol.parameters():
             p.add_(0.01 * torch.randn(p.shape, generator=g) * p.abs().mean())
     return pol, st, _cast(st, torch.float32)
-
-
-def _gen(seed=1):
-    import torch
-
-    return torch.Generator(device=DEV).manual_seed(seed)
 
 
 def _hip(pol, **kw):

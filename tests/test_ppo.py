@@ -1,11 +1,10 @@
 """The learner of robot_lab_amd/ppo.py (a restatement of rsl_rl's PPO.update; rsl-rl-lib itself is absent, so UNPINNED against the
 library): its pieces against their definitions, on CPU.  The end-to-end check - a robot learns to follow velocity commands on this
 simulator - is tests/test_gpu_train.py / tools/train_demo.py."""
-import types
-
 import numpy as np
 import torch
 
+from ppo_helpers import fake_storage as _fake_storage
 from robot_lab_amd.ppo import PPO, ActorCritic, gaussian_entropy, gaussian_kl, gaussian_log_prob
 
 
@@ -18,22 +17,6 @@ def test_gaussian_pieces_match_torch_distributions():
     torch.testing.assert_close(gaussian_log_prob(a, mu, sd), p.log_prob(a).sum(-1), rtol=1e-5, atol=1e-5)
     torch.testing.assert_close(gaussian_entropy(sd), p.entropy().sum(-1), rtol=1e-5, atol=1e-5)
     torch.testing.assert_close(gaussian_kl(mu, sd, mu2, sd2), torch.distributions.kl_divergence(p, q).sum(-1), rtol=1e-4, atol=1e-4)
-
-
-def _fake_storage(policy, T=8, N=64, od=10, cd=14, A=3, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, od, generator=g), torch.randn(T, N, cd, generator=g)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    # a batch in which action dimension 0 being positive is "good": the update must raise the policy's mean along it
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
 
 
 def test_update_follows_the_advantage_and_adapts_the_learning_rate():

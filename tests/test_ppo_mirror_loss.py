@@ -11,13 +11,15 @@ Agreement is held to fp64 round-off, measured in spacings of the tensor's larges
 (up to n_sym * 24 rows times up to 16 units) in different orders, every addition can leave half a spacing of a partial sum, and partial sums
 exceed the (cancelling) result by a small factor - ULPS = 4096 spacings, 9e-13 relative, the 1e-12 of tests/test_ppo_symmetry.py."""
 import copy
+import functools
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from robot_lab_amd.ppo import PPO, ActorCritic, gaussian_log_prob
+from ppo_helpers import fake_storage, tables
+from robot_lab_amd.ppo import PPO, ActorCritic
 from robot_lab_amd.symmetry import SymmetryTables
 
 T, N, OD, CD, A = 3, 8, 11, 7, 5
@@ -25,34 +27,8 @@ ROWS = T * N
 COEFF = 0.5
 ULPS = 4096
 KW = dict(num_learning_epochs=1, num_mini_batches=1, max_grad_norm=1e30)
-
-
-def _fake_storage(policy, seed=0):
-    """`_fake_storage` of tests/test_ppo.py in fp64 (action dimension 0 being positive is "good")"""
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, OD, generator=g, dtype=torch.float64), torch.randn(T, N, CD, generator=g, dtype=torch.float64)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g, dtype=torch.float64)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
-
-
-def _random_table(rng, n_sym, dim):
-    """random signed permutations, row 0 the identity: arbitrary gathers, independent of symmetry.py's builders"""
-    perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
-    sign = np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
-    return perm, sign
-
-
-def _tables(n_sym, seed=7):
-    rng = np.random.default_rng(seed)
-    return SymmetryTables(obs=_random_table(rng, n_sym, OD), critic=_random_table(rng, n_sym, CD), act=_random_table(rng, n_sym, A))
+_fake_storage = functools.partial(fake_storage, T=T, N=N, od=OD, cd=CD, A=A, dtype=torch.float64)
+_tables = functools.partial(tables, (OD, CD, A), seed=7)
 
 
 def _apply(table, s, x):

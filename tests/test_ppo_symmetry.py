@@ -5,14 +5,16 @@ of `ppo.PPO(symmetry=...)` against the materialised construction: today's plain 
 tests/test_gpu_ppo_hip_symmetry.py."""
 import copy
 import dataclasses
+import functools
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from ppo_helpers import fake_storage, random_table as _random_table
 from robot_lab_amd.desc import OBS_KINDS, arr
-from robot_lab_amd.ppo import PPO, ActorCritic, gaussian_kl, gaussian_log_prob
+from robot_lab_amd.ppo import PPO, ActorCritic, gaussian_kl
 from robot_lab_amd.scene import load_bundle
 from robot_lab_amd.symmetry import _VEC, SymmetryTables, tables_for_env
 
@@ -162,29 +164,7 @@ def test_symmetry_tables_validation():
 # ---- the rule against the materialised construction ------------------------------------------------------------------------------------
 T, N, OD, CD, A, NSYM = 4, 24, 45, 235, 12, 3
 ROWS = T * N  # 96
-
-
-def _fake_storage(policy, seed=0):
-    """`_fake_storage` of tests/test_ppo.py in fp64 (action dimension 0 being positive is "good")"""
-    g = torch.Generator().manual_seed(seed)
-    obs, cobs = torch.randn(T, N, OD, generator=g, dtype=torch.float64), torch.randn(T, N, CD, generator=g, dtype=torch.float64)
-    with torch.no_grad():
-        mu, sd = policy.distribution(obs)
-        act = mu + sd * torch.randn(mu.shape, generator=g, dtype=torch.float64)
-        logp = gaussian_log_prob(act, mu, sd)
-        val = policy.critic(cobs).squeeze(-1)
-    adv = act[..., 0].clone()
-    adv = (adv - adv.mean()) / adv.std()
-    ret = val + adv
-    return types.SimpleNamespace(num_transitions_per_env=T, num_envs=N, observations=obs, privileged_observations=cobs, actions=act, values=val.unsqueeze(-1),
-                                 returns=ret.unsqueeze(-1), advantages=adv.unsqueeze(-1), actions_log_prob=logp.unsqueeze(-1), mu=mu, sigma=sd.expand_as(mu).contiguous())
-
-
-def _random_table(rng, n_sym, dim):
-    """random signed permutations, row 0 the identity: arbitrary gathers, independent of symmetry.py's builders"""
-    perm = np.stack([np.arange(dim)] + [rng.permutation(dim) for _ in range(n_sym - 1)]).astype(np.int32)
-    sign = np.concatenate([np.ones((1, dim)), rng.choice([-1.0, 1.0], size=(n_sym - 1, dim))]).astype(np.float32)
-    return perm, sign
+_fake_storage = functools.partial(fake_storage, T=T, N=N, od=OD, cd=CD, A=A, dtype=torch.float64)
 
 
 def _materialise(st, tab):
