@@ -50,7 +50,7 @@ struct MlpParams {
 __device__ inline float activate(float v, int act) {
   switch (act) {
     case RL_ACT_ELU: return v > 0.f ? v : __expf(v) - 1.0f;  // |abs error| ~1e-7: inside the fp32 round-off of the layer
-    case RL_ACT_RELU: return fmaxf(v, 0.f);
+    case RL_ACT_RELU: return v < 0.f ? 0.f : v;  // (not fmaxf: that returns 0 for a NaN, torch.relu and the oracle pass it on)
     default: return tanhf(v);
   }
 }
@@ -179,7 +179,7 @@ __device__ inline void layer(const MlpParams& P, int l, const float* __restrict_
         continue;
 #endif
         if (!last) {
-          const float av = act == RL_ACT_ELU ? (v > 0.f ? v : __expf(v) - 1.0f) : act == RL_ACT_RELU ? fmaxf(v, 0.f) : tanhf(v);
+          const float av = act == RL_ACT_ELU ? (v > 0.f ? v : __expf(v) - 1.0f) : act == RL_ACT_RELU ? (v < 0.f ? 0.f : v) : tanhf(v);
           xout[rt * TILE + obase + 256 * WAVES * t + 4 * r] = valid ? av : 0.f;  // padded columns feed zeros into the next layer
         } else if (valid && row0 + rt * MT + rbase + r < n_rows) {
           y[(size_t)(row0 + rt * MT + rbase + r) * P.out_dim + n] = v;
@@ -354,8 +354,12 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_fused_pair_kernel(MlpPair q, i
 // (16x the f32 MFMA rate per flop) replace 8 k-steps of v_mfma_f32_16x16x4_f32: 16 / 6 = 2.7x the contraction rate of the exact
 // f32 path, and the result is NOT lower precision - the three dropped products are below fp32 round-off of the term, and the sum
 // sees one fp32 rounding per 32-deep block instead of one per k (measured on the A1 networks against the fp64 oracle: max |err|
-// 8e-7 vs 2e-6 for an fp32 fmaf chain; tests/test_policy.py keeps rtol = atol = 2e-5).  The small products accumulate in their
-// own registers so that they are not rounded away against the running main sum.
+// 8e-7 vs 2e-6 for an fp32 fmaf chain).  What the tests hold it to: max |err| <= 8 x the distance of a numpy fp32 forward from the
+// fp64 oracle on every route (tests/policy_helpers.py M_BOUND; the kernels measure 0.4 - 2.0 x, a single missing plane product 35 x
+// or more: profiles/mlp_accuracy.txt, tests/test_policy_exact.py), and bit equality on networks whose sums are exact
+// (tests/test_gpu_policy_exact.py).  Floor: inputs and activations of magnitude >= 2^-100 - below it the `lo` plane (24 bits
+// further down) becomes a denormal bf16 and the three planes stop summing to x in the matrix core.  The small products accumulate
+// in their own registers so that they are not rounded away against the running main sum.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct Split3 {
@@ -492,7 +496,7 @@ __device__ inline void layer_s(const MlpParams& P, int l, const uint16_t* __rest
       for (int r = 0; r < 4; ++r) {
         const float v = ((acc[rt][t][1][r] + acc[rt][t][2][r]) + acc[rt][t][0][r]) + bias;
         if (!last) {
-          const float av = act == RL_ACT_ELU ? (v > 0.f ? v : __expf(v) - 1.0f) : act == RL_ACT_RELU ? fmaxf(v, 0.f) : tanhf(v);
+          const float av = act == RL_ACT_ELU ? (v > 0.f ? v : __expf(v) - 1.0f) : act == RL_ACT_RELU ? (v < 0.f ? 0.f : v) : tanhf(v);
           const Split3 sp = split3(valid ? av : 0.f);  // padded columns feed zeros into the next layer
           if (in_layer) {
             uint16_t* xo = xout + rt * tstride_out + o + 8 * r;

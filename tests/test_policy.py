@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle.policy import mlp_forward
+from policy_helpers import assert_bits_equal, assert_fp32_bound
 from robot_lab_amd.policy import POLICY_EXPORTS, POLICY_LIB
 
 
@@ -72,15 +73,19 @@ def test_hip_mlp_matches_oracle(dims, act, N, prec, monkeypatch):
     want = mlp_forward(x, ws, bs, act)
     # exact-fp32 MFMA = a k-ordered fmaf chain: round-off of a K <= 512 dot product; the split path sees fewer roundings
     np.testing.assert_allclose(got, want, rtol=2e-5, atol=2e-5)
+    # the bound that sees a missing split product: a small multiple of a numpy fp32 forward's own distance from the oracle
+    # (tests/policy_helpers.py M_BOUND; its teeth: tests/test_policy_exact.py)
+    assert_fp32_bound(got, x, ws, bs, act, f"{dims} {act} x {N}, {prec or 'split-bf16'}", want)
     err = np.abs(got - want) / (1.0 + np.abs(want))
     print(f"\n[mlp {prec or 'split-bf16'}] {dims} x {N}: max |err| / (1 + |y|) = {err.max():.2e}")
     pol.close()
 
 
 @pytest.mark.gpu
-def test_split_path_survives_large_and_tiny_values():
+def test_split_path_survives_large_and_tiny_values(monkeypatch):
     """The bf16 planes keep fp32's exponent range: activations of 1e4 and inputs of 1e-20 go through the split path like through
-    the f32 kernels (an fp16 split would overflow / flush them)."""
+    the f32 kernels (an fp16 split would overflow / flush them).  The absolute tolerance says nothing about the 1e-20 rows, so the range
+    is pinned by homogeneity: without biases a relu network commutes with a power of two, f(2^s x) = 2^s f(x) bit for bit."""
     import torch
 
     from robot_lab_amd.policy import MlpPolicy
@@ -96,6 +101,18 @@ def test_split_path_survives_large_and_tiny_values():
     want = mlp_forward(x, ws, bs, "relu")
     assert np.abs(want).max() > 1e3
     np.testing.assert_allclose(got, want, rtol=2e-5, atol=2e-5)
+    # (on the batch before its 1e-20 rows: 2^-60 times those would put the `lo` plane below the split path's floor of 2^-100 - 24 bits)
+    pol.set_weights(ws, [np.zeros_like(b) for b in bs])
+    x0 = np.random.default_rng(12).uniform(-30, 30, (64, 40)).astype(np.float32)
+    assert np.abs(x0).min() * 2.0 ** -60 >= 2.0 ** -100
+    xt = torch.from_numpy(x0).cuda()
+    for prec in PRECISIONS:
+        monkeypatch.setenv("RL_MLP_PRECISION", prec) if prec else monkeypatch.delenv("RL_MLP_PRECISION", raising=False)
+        base = pol(xt).cpu().numpy()
+        assert np.abs(base).max() > 1e3
+        for s in (-60, -20, 20, 60):
+            scaled = pol(torch.from_numpy(np.ldexp(x0, s)).cuda()).cpu().numpy()  # (np.ldexp: exact)
+            assert_bits_equal(scaled, np.ldexp(base, s), f"{prec or 'split-bf16'}: f(2^{s} x) against 2^{s} f(x)")
     pol.close()
 
 
