@@ -35,9 +35,19 @@ class Collector:
 
     def __init__(self, env, actor, critic, storage, action_std: torch.Tensor, gamma: float = 0.99, lam: float = 0.95,
                  normalize_advantage: bool = True, use_graph: bool = True, clip_actions: float | None = None, overlap: bool = False, critic_small: bool = True,
-                 fused_act: bool = True):
+                 fused_act: bool = True, normalizers=None):
         self.env, self.actor, self.critic, self.storage = env, actor, critic, storage
         self.overlap = overlap
+        # (actor_norm | None, critic_norm | None): robot_lab_amd.obsnorm.ObsNormalizer handles of the two observation groups - see `_iteration_normalized`
+        self.normalizers = tuple(normalizers) if normalizers is not None and any(n is not None for n in normalizers) else None
+        if self.normalizers is not None:
+            if len(self.normalizers) != 2:
+                raise ValueError("Collector: normalizers is (actor_norm | None, critic_norm | None)")
+            if overlap:
+                raise NotImplementedError("Collector: overlap=True with observation normalisation is not implemented: the critic's side stream would read the "
+                                          "statistics while the main stream's update of the same step rewrites them; use the serial loop (overlap=False)")
+            obs0 = env.get_observations()
+            self._norm_obs = tuple(None if n is None else torch.empty_like(obs0[k]) for n, k in zip(self.normalizers, ("policy", "critic")))
         # sampling / log-prob / the slot's first half in the epilogue of the actor + critic launch (include/rl_act.h): one launch and one gap
         # less per step than actor + critic, then `act` (second half); same storage bit for bit (tests/test_gpu_collect.py)
         self.fused_act = fused_act
@@ -55,6 +65,8 @@ class Collector:
     def _iteration(self, obs):
         if self.overlap:
             return self._iteration_overlapped(obs)
+        if self.normalizers is not None:
+            return self._iteration_normalized(obs)
         st, env = self.storage, self.env
         st.clear()
         for _ in range(self.T):
@@ -67,6 +79,39 @@ class Collector:
                     actions = actions.clamp(-self.clip_actions, self.clip_actions)
             obs, _, _, _, _ = env.step(actions, rollout=st, gamma=self.gamma)
         st.compute_returns(self.critic(obs["critic"]), self.gamma, self.lam, self.normalize)
+        return obs
+
+    def _normalized(self, obs):
+        """(policy rows, critic rows) as the networks see them: normalised into the collector's scratch where the group has a normaliser"""
+        (an, cn), (sp, sc) = self.normalizers, self._norm_obs
+        if an is not None and cn is not None:
+            return an.apply_pair(obs["policy"], cn, obs["critic"], out=sp, other_out=sc)
+        if an is not None:
+            return an.apply(obs["policy"], out=sp), obs["critic"]
+        return obs["policy"], cn.apply(obs["critic"], out=sc)
+
+    def _iteration_normalized(self, obs):
+        """rsl_rl's order with `actor_obs_normalization` / `critic_obs_normalization` (`PPO.act`, then `process_env_step`): the networks see
+        normalizer(obs_t), the storage keeps the RAW rows (`act`, the unfused route: the slot's packing does not change), and after env.step
+        the statistics take the NEW observations obs_{t+1} - so the first observation after reset() never enters them, and the critic call
+        of `compute_returns` sees statistics that already contain obs_T.  Three launches per step more than the fused-act loop
+        (apply, act, update); fusing the normalisation into the first layer's operand fetch would give them back."""
+        st, env = self.storage, self.env
+        an, cn = self.normalizers
+        st.clear()
+        for _ in range(self.T):
+            p, c = self._normalized(obs)
+            mean, values = self.actor.forward_pair(p, self.critic, c)
+            actions = st.act(obs["policy"], obs["critic"], mean, self.std, values)
+            if self.clip_actions is not None:
+                actions = actions.clamp(-self.clip_actions, self.clip_actions)
+            obs, _, _, _, _ = env.step(actions, rollout=st, gamma=self.gamma)
+            if an is not None and cn is not None:
+                an.update_pair(obs["policy"], cn, obs["critic"])
+            else:
+                (an or cn).update(obs["policy" if an is not None else "critic"])
+        last = obs["critic"] if cn is None else cn.apply(obs["critic"], out=self._norm_obs[1])
+        st.compute_returns(self.critic(last), self.gamma, self.lam, self.normalize)
         return obs
 
     def _iteration_overlapped(self, obs):

@@ -13,6 +13,7 @@ library (no copy of it exists here); `tests/test_ppo.py` checks the pieces again
 and it is what makes `tools/train_demo.py` - the end-to-end check that the simulator is a learnable environment - possible."""
 from __future__ import annotations
 
+import functools
 import math
 import numbers
 
@@ -29,20 +30,69 @@ def mlp(dims, activation=nn.ELU):
     return nn.Sequential(*layers)
 
 
+class EmpiricalNormalization(nn.Module):
+    """THE RULE of the observation normalisation (rsl_rl `EmpiricalNormalization`): running mean and POPULATION variance of the rows it
+    is shown, `forward(x) = (x - _mean) / (_std + eps)`.  The device half is csrc/rl_obsnorm.hip (include/rl_obsnorm.h), checked against
+    this module; buffer names and shapes are rsl_rl's, so `state_dict()` keys are `<name>._mean`, `._var`, `._std`, `.count`."""
+
+    def __init__(self, dim, eps=1e-2):
+        super().__init__()
+        self.eps = eps
+        self.register_buffer("_mean", torch.zeros(1, dim))
+        self.register_buffer("_var", torch.ones(1, dim))
+        self.register_buffer("_std", torch.ones(1, dim))
+        self.register_buffer("count", torch.tensor(0, dtype=torch.long))
+
+    def forward(self, x):
+        return (x - self._mean) / (self._std + self.eps)
+
+    @torch.no_grad()
+    def update(self, x):
+        """Chan's merge of the state with the batch `x` [n, dim]; nothing happens outside training mode."""
+        if not self.training:
+            return
+        n = x.shape[0]
+        self.count += n
+        rate = torch.tensor(n, dtype=torch.float32) / self.count.to(torch.float32)  # one fp32 division
+        rate = rate.to(device=self._mean.device, dtype=self._mean.dtype)
+        var_x, mean_x = torch.var_mean(x, dim=0, unbiased=False, keepdim=True)
+        delta = mean_x - self._mean
+        self._mean += rate * delta
+        self._var += rate * (var_x - self._var + delta * (mean_x - self._mean))
+        self._std = torch.sqrt(self._var)
+
+
 class ActorCritic(nn.Module):
     """rsl_rl `ActorCritic` as the cfg builds it (rsl_rl_ppo_cfg.py:15-22): two ELU MLPs, a state-independent standard deviation
-    (`noise_std_type="scalar"`, init 1.0), no observation normalisation.  `state_dict()` keys follow rsl_rl (`actor.<2l>.weight`,
-    `critic.<2l>.weight`, `std`), so checkpoints load into `robot_lab_amd.policy.MlpPolicy.from_state_dict` and the shim's exporters."""
+    (`noise_std_type="scalar"`, init 1.0).  `state_dict()` keys follow rsl_rl (`actor.<2l>.weight`, `critic.<2l>.weight`, `std`), so
+    checkpoints load into `robot_lab_amd.policy.MlpPolicy.from_state_dict` and the shim's exporters.
+    `actor_obs_normalization` / `critic_obs_normalization`: `actor_obs_normalizer` / `critic_obs_normalizer` are an
+    `EmpiricalNormalization` when the flag is on and `nn.Identity()` (no keys) when it is off; neither has a trainable parameter."""
 
-    def __init__(self, obs_dim, critic_obs_dim, act_dim, actor_hidden=(512, 256, 128), critic_hidden=(512, 256, 128), init_noise_std=1.0):
+    def __init__(self, obs_dim, critic_obs_dim, act_dim, actor_hidden=(512, 256, 128), critic_hidden=(512, 256, 128), init_noise_std=1.0,
+                 actor_obs_normalization=False, critic_obs_normalization=False):
         super().__init__()
         self.actor = mlp([obs_dim, *actor_hidden, act_dim])
         self.critic = mlp([critic_obs_dim, *critic_hidden, 1])
         self.std = nn.Parameter(init_noise_std * torch.ones(act_dim))
+        self.actor_obs_normalization, self.critic_obs_normalization = bool(actor_obs_normalization), bool(critic_obs_normalization)
+        self.actor_obs_normalizer = EmpiricalNormalization(obs_dim) if actor_obs_normalization else nn.Identity()
+        self.critic_obs_normalizer = EmpiricalNormalization(critic_obs_dim) if critic_obs_normalization else nn.Identity()
 
-    def distribution(self, obs):
-        mean = self.actor(obs)
+    def distribution(self, obs, normalized=False):
+        """`normalized`: `obs` went through the actor's normaliser already"""
+        mean = self.actor(obs if normalized else self.actor_obs_normalizer(obs))
         return mean, self.std.expand_as(mean)
+
+    def evaluate(self, critic_obs):
+        return self.critic(self.critic_obs_normalizer(critic_obs))
+
+    def update_normalization(self, obs, critic_obs):
+        """rsl_rl `ActorCritic.update_normalization`, what `process_env_step` calls with the NEW observations"""
+        if self.actor_obs_normalization:
+            self.actor_obs_normalizer.update(obs)
+        if self.critic_obs_normalization:
+            self.critic_obs_normalizer.update(critic_obs)
 
 
 def gaussian_log_prob(actions, mean, std):
@@ -139,6 +189,12 @@ class PPO:
         logp_old, mu_old, sigma_old = flat(storage.actions_log_prob).view(-1), flat(storage.mu), flat(storage.sigma)
         B = T * N
         mb = B // self.num_mini_batches
+        # THE RULE with observation normalisation: actor(actor_obs_normalizer(obs)), critic(critic_obs_normalizer(critic_obs)) on the RAW stored rows.
+        # A batch that says `obs_normalized` (Trainer's `NormalizedBatch`: both matrices already went through rl_obsnorm_apply, same bits as
+        # the modules' forward) meets the networks directly.
+        distribution, critic = self.policy.distribution, self.policy.evaluate
+        if getattr(storage, "obs_normalized", False):
+            distribution, critic = functools.partial(distribution, normalized=True), self.policy.critic
         stats = dict(value_loss=0.0, surrogate_loss=0.0, entropy=0.0, kl=0.0)
         if self.mirror_loss is not None:
             stats["mirror_loss"] = 0.0
@@ -156,13 +212,13 @@ class PPO:
                     mb_obs, mb_cobs, mb_actions = self._mirrored("obs", obs[idx]), self._mirrored("critic", cobs[idx]), self._mirrored("act", actions[idx])
                     rep = idx.repeat(self.symmetry.n_sym)  # the stored row of every one of the n_sym n rows
                 n = idx.numel()
-                mean, std = self.policy.distribution(mb_obs)
+                mean, std = distribution(mb_obs)
                 if self.mirror_loss is not None:
                     mirror = ((mean[n:] - self._mirrored("act", mean[:n].detach())[n:]) ** 2).mean()
                     if not self.data_augmentation:
                         mean, std = mean[:n], std[:n]
                 logp = gaussian_log_prob(mb_actions, mean, std)
-                value = self.policy.critic(mb_cobs).view(-1)
+                value = critic(mb_cobs).view(-1)
                 entropy = gaussian_entropy(std)
                 if self.schedule == "adaptive" and self.desired_kl is not None:
                     with torch.inference_mode():
@@ -215,6 +271,27 @@ def mirror_repr(alg):
     return f", mirror_loss={alg.mirror_loss:g}" + ("" if alg.data_augmentation else ", data_augmentation=False")
 
 
+class NormalizedBatch:
+    """A filled `RolloutStorage` as the learners read it, with `observations` / `privileged_observations` replaced by matrices that
+    `normalize()` fills with `rl_obsnorm_apply` over all T N stored rows (a group without normaliser keeps the storage's own tensor);
+    every other attribute is the storage's.  `obs_normalized` tells `PPO.update` that the modules' forward has been applied already."""
+    obs_normalized = True
+
+    def __init__(self, storage, normalizers):
+        self._storage, self._normalizers = storage, normalizers
+        raw = (storage.observations, storage.privileged_observations)
+        self._raw = raw
+        self.observations, self.privileged_observations = (r if h is None else torch.empty_like(r) for r, h in zip(raw, normalizers))
+
+    def __getattr__(self, name):
+        return getattr(self._storage, name)
+
+    def normalize(self):
+        for h, r, out in zip(self._normalizers, self._raw, (self.observations, self.privileged_observations)):
+            if h is not None:
+                h.apply(r.view(-1, r.shape[-1]), out=out.view(-1, out.shape[-1]))
+
+
 MAX_INPUT_WIDTH = 512  # = RL_MLP_MAX_WIDTH (include/rl_policy.h) = RL_PPO_MAX_WIDTH (include/rl_ppo.h): widest layer, the input included
 
 
@@ -225,10 +302,16 @@ class Trainer:
     `symmetry`: symmetry data augmentation inside the update of either learner - a `symmetry.SymmetryTables`, or the mirrors of this
     env's robot ("lr", "fb", "lr,fb" or a tuple of them), resolved with `symmetry.tables_for_env(env)`.
     `mirror_loss=c`, `data_augmentation=False` (with `symmetry`; forwarded to the learner): rsl_rl's mirror loss on the same tables, with
-    or without the augmentation - the rule is `PPO.update`'s."""
+    or without the augmentation - the rule is `PPO.update`'s.
+    `actor_obs_normalization`, `critic_obs_normalization`: rsl_rl's empirical normalisation of the group (`EmpiricalNormalization` is the
+    rule, csrc/rl_obsnorm.hip runs it): statistics updated inside the captured collection loop with the NEW observations of every step,
+    applied in front of both networks there, and once per update over the stored RAW rows with the statistics as the collection left
+    them.  `state_dict()` gains rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` keys.  Refused with `symmetry` and with a
+    `group` of more than one rank."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
-                 critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None, **ppo_kw):
+                 critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None,
+                 actor_obs_normalization=False, critic_obs_normalization=False, **ppo_kw):
         from .collect import Collector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
@@ -241,9 +324,22 @@ class Trainer:
                 raise ValueError(f"Trainer: the {name} observation row is {width} columns wide" + (f" (observation history {hist})" if hist else "") +
                                  f", the fused inference kernels and the HIP learner take at most {MAX_INPUT_WIDTH} input columns: shorten the "
                                  f"{name} group's history_length or drop terms from it")
+        normalized = tuple(name for name, on in (("policy", actor_obs_normalization), ("critic", critic_obs_normalization)) if on)
+        if normalized and symmetry is not None:
+            raise NotImplementedError("Trainer: symmetry= together with observation normalisation is not implemented: rsl_rl normalises the MIRRORED raw row, "
+                                      "which is not the mirror of the normalised row unless the statistics are symmetric, and the learners mirror inside "
+                                      "their first layer's operand fetch, behind the normalisation (drop symmetry=, or the *_obs_normalization flags)")
+        if normalized and group is not None and getattr(group, "world_size", 1) > 1:
+            raise NotImplementedError(f"Trainer: observation normalisation with a group of {group.world_size} ranks is not implemented: whether the ranks "
+                                      "keep their own statistics or reduce them is not decided here (run one rank, or drop the *_obs_normalization flags)")
         torch.manual_seed(seed)
         self.env, self.device = env, obs["policy"].device
-        self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std).to(self.device)
+        if normalized:
+            self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std, bool(actor_obs_normalization),
+                                      bool(critic_obs_normalization)).to(self.device)
+        else:
+            self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std).to(self.device)
+        self.normalized = normalized
         if learner not in ("torch", "hip"):
             raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
         self.learner = learner
@@ -274,21 +370,51 @@ class Trainer:
         self.critic = MlpPolicy([host(x.weight) for x in lin(self.policy.critic)], [host(x.bias) for x in lin(self.policy.critic)], "elu", device=str(self.device))
         self.storage = RolloutStorage(env.num_envs, num_steps_per_env, od, cd, A, seed=seed, device=str(self.device))
         self.std = self.policy.std.detach().clone()  # the tensor the sampling kernel reads: refreshed in place after every update
-        self.collector = Collector(env, self.actor, self.critic, self.storage, self.std, gamma=gamma, lam=lam, use_graph=use_graph, clip_actions=clip_actions)
+        self.normalizers, self._batch = None, self.storage
+        if normalized:  # the device half of the policy's EmpiricalNormalization modules + the update's normalised [T N, dim] matrices
+            from .obsnorm import ObsNormalizer
+
+            mods = (self.policy.actor_obs_normalizer, self.policy.critic_obs_normalizer)
+            self.normalizers = tuple(ObsNormalizer(m._mean.shape[1], m.eps, max_rows=env.num_envs, device=str(self.device)) if isinstance(m, EmpiricalNormalization)
+                                     else None for m in mods)
+            self._batch = NormalizedBatch(self.storage, self.normalizers)
+            self.collector = Collector(env, self.actor, self.critic, self.storage, self.std, gamma=gamma, lam=lam, use_graph=use_graph, clip_actions=clip_actions,
+                                       normalizers=self.normalizers)
+        else:
+            self.collector = Collector(env, self.actor, self.critic, self.storage, self.std, gamma=gamma, lam=lam, use_graph=use_graph, clip_actions=clip_actions)
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self.iteration = 0
 
     def __repr__(self):
         sym = f", symmetry={self.symmetry!r}{mirror_repr(self.alg)}" if self.symmetry is not None else ""
+        sym += f", obs_normalization={list(self.normalized)}" if self.normalized else ""
         return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration}{sym})"
 
+    def _modules(self):
+        return (self.policy.actor_obs_normalizer, self.policy.critic_obs_normalizer)
+
+    def sync_normalizers(self):
+        """the normalisers' device state into the policy's `EmpiricalNormalization` buffers (stream-ordered, no wait)"""
+        for h, m in zip(self.normalizers or (), self._modules()):
+            if h is not None:
+                h.store_module(m)
+
     def state_dict(self):
-        """rsl_rl's `ActorCritic.state_dict()` layout; the HIP learner's master parameters are copied back into the module first."""
+        """rsl_rl's `ActorCritic.state_dict()` layout; the HIP learner's master parameters and the normalisers' device state are copied
+        back into the module first."""
         if self.learner == "hip":
             self.alg.store_into(self.policy)
+        self.sync_normalizers()
         return self.policy.state_dict()
 
     def push_parameters(self):
+        """the module's parameters into the inference kernels and - after a `load_state_dict` - its normaliser buffers into the handles"""
+        self._push_weights()
+        for h, m in zip(self.normalizers or (), self._modules()):
+            if h is not None:
+                h.load_module(m)
+
+    def _push_weights(self):
         if self.learner == "hip":
             # Device to device on the CURRENT stream, with no device-wide wait (unlike rl_mlp_set_weights below).  Ordering relied on: the update
             # ran on this stream, so the push follows it; the next collection - eager or the captured graph - is launched on this same stream, so
@@ -300,12 +426,20 @@ class Trainer:
         self.critic.load_linear_layers(self.policy.critic)
         self.std.copy_(self.policy.std.detach().clamp_min(1e-6))
 
+    def update_batch(self):
+        """the filled storage as the learner reads it: the storage itself, or - with observation normalisation - a `NormalizedBatch` whose two
+        observation matrices hold the stored raw rows through the statistics as the collection left them (one `apply` per group)"""
+        if self.normalized:
+            self._batch.normalize()
+            self.sync_normalizers()  # (`alg.policy`'s buffers stay current: the torch rule, exporters and checkpoints read them)
+        return self._batch
+
     def iterate(self) -> dict:
         self.collector.collect()
         st = self.storage
         out = dict(mean_reward=float(st.rewards.mean()), done_rate=float(st.dones.float().mean()))
-        out.update(self.alg.update(st, self.gen))
-        self.push_parameters()
+        out.update(self.alg.update(self.update_batch(), self.gen))
+        self._push_weights()
         out["action_std"] = float((self.std if self.learner == "hip" else self.policy.std.detach()).mean())
         self.iteration += 1
         return out

@@ -7,7 +7,9 @@
 `env` is the `RslRlVecEnvWrapper` of the shims around `robot_lab_amd.env.ManagerBasedRLEnv`.  Collection runs on the HIP kernels as
 one hipGraph launch per iteration (robot_lab_amd/collect.py), the update is robot_lab_amd/ppo.py - or, with `RL_LEARNER=hip` in the
 environment, the HIP learner of robot_lab_amd/ppo_hip.py, on one GPU or under `--distributed` -, checkpoints use rsl_rl's layout
-(`model_<it>.pt`: model_state_dict / optimizer_state_dict / iter / infos) with either learner, and one learner's checkpoint resumes the other."""
+(`model_<it>.pt`: model_state_dict / optimizer_state_dict / iter / infos) with either learner, and one learner's checkpoint resumes the other.
+`policy.actor_obs_normalization` / `policy.critic_obs_normalization` reach the `Trainer` (csrc/rl_obsnorm.hip); the checkpoint then carries
+rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` buffers."""
 from __future__ import annotations
 
 import os
@@ -33,8 +35,10 @@ class OnPolicyRunner:
         pol, alg = dict(train_cfg.get("policy", {})), dict(train_cfg.get("algorithm", {}))
         if pol.get("class_name", "ActorCritic") != "ActorCritic" or alg.get("class_name", "PPO") != "PPO":
             raise NotImplementedError(f"stand-in runner: ActorCritic + PPO only, got {pol.get('class_name')} / {alg.get('class_name')}")
-        if pol.get("activation", "elu") != "elu" or pol.get("actor_obs_normalization") or pol.get("critic_obs_normalization"):
-            raise NotImplementedError("stand-in runner: ELU networks without observation normalisation (what every robot_lab agent cfg uses)")
+        if pol.get("activation", "elu") != "elu":
+            raise NotImplementedError("stand-in runner: ELU networks only (what every robot_lab agent cfg uses)")
+        # rsl_rl's empirical observation normalisation per group: robot_lab_amd.ppo.EmpiricalNormalization on csrc/rl_obsnorm.hip
+        norm = dict(actor_obs_normalization=bool(pol.get("actor_obs_normalization")), critic_obs_normalization=bool(pol.get("critic_obs_normalization")))
         sym = alg.get("symmetry_cfg")
         if sym:
             get = sym.get if isinstance(sym, dict) else lambda k, d=None: getattr(sym, k, d)  # noqa: E731
@@ -52,8 +56,11 @@ class OnPolicyRunner:
                                       f"robot_lab velocity cfg but ANYmal-D's uses) is wired to the fused inference kernels")
         if pol.get("noise_std_type", "scalar") != "scalar":
             raise NotImplementedError(f"stand-in runner: noise_std_type={pol.get('noise_std_type')!r}; the sampling kernel reads a scalar-type std vector")
-        if train_cfg.get("empirical_normalization") or alg.get("normalize_advantage_per_mini_batch"):
-            raise NotImplementedError("stand-in runner: empirical_normalization / normalize_advantage_per_mini_batch are not implemented")
+        if train_cfg.get("empirical_normalization"):
+            raise NotImplementedError("stand-in runner: the runner-level empirical_normalization is rsl_rl's deprecated spelling and is not read here: set "
+                                      "policy.actor_obs_normalization=True and policy.critic_obs_normalization=True, which mean the same")
+        if alg.get("normalize_advantage_per_mini_batch"):
+            raise NotImplementedError("stand-in runner: normalize_advantage_per_mini_batch is not implemented")
         # one process per GPU (README.md:323-337, train.py:143-150): rsl_rl's multi-GPU contract lives in robot_lab_amd/dist.py.  A world of
         # N ranks whose learners were not tied together would be N unrelated trainings writing over each other's logs - never run that.
         from robot_lab_amd.dist import LearnerGroup
@@ -65,7 +72,7 @@ class OnPolicyRunner:
                                lam=float(alg.get("lam", 0.95)), seed=int(train_cfg.get("seed", 42)), actor_hidden=pol.get("actor_hidden_dims", (512, 256, 128)),
                                critic_hidden=pol.get("critic_hidden_dims", (512, 256, 128)), init_noise_std=float(pol.get("init_noise_std", 1.0)),
                                clip_actions=getattr(env, "clip_actions", None), group=self.group if self.group.enabled else None, learner=self.learner,
-                               **{k: alg[k] for k in keys if k in alg})
+                               **{k: v for k, v in norm.items() if v}, **{k: alg[k] for k in keys if k in alg})
         self.alg = self.trainer.alg
         self.alg.policy.reset = lambda dones=None: None  # feed-forward policy: nothing to reset (play.py:246)
         self.save_interval = int(train_cfg.get("save_interval", 50))
@@ -127,12 +134,13 @@ class OnPolicyRunner:
             optimizer_state = self.alg.optimizer_state_dict()
         else:
             optimizer_state = self.alg.optimizer.state_dict()
+        self.trainer.sync_normalizers()  # the running statistics live on the device: into the module's buffers (rsl_rl's keys)
         torch.save({"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": optimizer_state,
                     "iter": self.current_learning_iteration, "infos": infos}, path)
 
     def load(self, path: str, load_optimizer: bool = True, map_location=None):
         d = torch.load(path, map_location=map_location or self.trainer.device, weights_only=False)
-        self.alg.policy.load_state_dict(d["model_state_dict"])
+        self.alg.policy.load_state_dict(d["model_state_dict"])  # strict: normaliser keys the flags do not ask for - or miss - raise here
         if self.learner == "hip":
             self.alg.load_from(self.alg.policy)
             if load_optimizer and d.get("optimizer_state_dict"):
@@ -140,14 +148,18 @@ class OnPolicyRunner:
         elif load_optimizer and d.get("optimizer_state_dict"):
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
         self.current_learning_iteration = int(d.get("iter", 0))
-        self.trainer.push_parameters()
+        self.trainer.push_parameters()  # (the normalisers' buffers go to their handles with it)
         return d.get("infos")
 
     def get_inference_policy(self, device=None):
         actor = self.trainer.actor  # the fused HIP inference kernel (csrc/rl_policy.hip), fed by push_parameters()
+        norm = (self.trainer.normalizers or (None, None))[0]  # the actor group's statistics are applied, never updated (rsl_rl `act_inference`)
 
         def policy(obs):
-            return actor(obs if torch.is_tensor(obs) else obs["policy"])
+            obs = obs if torch.is_tensor(obs) else obs["policy"]
+            if norm is not None:
+                obs = norm.apply(obs.to(device=norm.device, dtype=torch.float32).contiguous())
+            return actor(obs)
 
         return policy
 

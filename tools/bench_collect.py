@@ -5,8 +5,10 @@
 then alg.compute_returns(obs) - every piece on the HIP kernels of this repo (actor + critic: rl_policy.hip, noise /
 log-prob / storage / GAE: rl_rollout.hip, env: rl_env.hip).  Random network weights: the arithmetic does not
 depend on them.
-    python tools/bench_collect.py [task] [num_envs] [iterations] [--obs-history N]
---obs-history N: policy-group observation history of N frames, measured against history off in alternating windows of this process."""
+    python tools/bench_collect.py [task] [num_envs] [iterations] [--obs-history N] [--obs-normalization]
+--obs-history N: policy-group observation history of N frames, measured against history off in alternating windows of this process.
+--obs-normalization: empirical normalisation of both groups (csrc/rl_obsnorm.hip) against the fused-act loop and against the unfused loop
+(actor + critic, then the act kernel) it is built on, alternating windows of this process."""
 import os
 import sys
 import time
@@ -24,6 +26,9 @@ if "--obs-history" in sys.argv:  # --obs-history N: policy-group observation his
     i = sys.argv.index("--obs-history")
     ap_hist = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+ap_norm = "--obs-normalization" in sys.argv
+if ap_norm:
+    sys.argv.remove("--obs-normalization")
 task = sys.argv[1] if len(sys.argv) > 1 else "RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0"
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 ITERS = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -36,8 +41,8 @@ FUSED_ACT = os.environ.get("RL_FUSED_ACT", "1") == "1"  # sampling / log-prob / 
 OVERLAP = os.environ.get("RL_OVERLAP", "0") == "1"  # the critic of step t on a second stream under env step t (0: actor + critic as one launch in front of act)
 
 
-def setup(hist):
-    """-> (env, storage, iteration(obs) -> obs) of one collection loop; `hist`: policy-group history length (0: none)"""
+def setup(hist, norm=False, fused_act=FUSED_ACT):
+    """-> (env, storage, iteration(obs) -> obs) of one collection loop; `hist`: policy-group history length (0: none); `norm`: both groups normalised"""
     env = ManagerBasedRLEnv(task, num_envs=N, seed=42, device="cuda:0", obs_history={"policy": hist} if hist else None)
     obs, _ = env.reset()
     od, cd, A = obs["policy"].shape[1], obs["critic"].shape[1], env.num_actions
@@ -53,8 +58,15 @@ def setup(hist):
     if GRAPH and FUSED and PAIR:
         from robot_lab_amd.collect import Collector  # noqa: E402
 
-        col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, overlap=OVERLAP, critic_small=SMALL, fused_act=FUSED_ACT)
-        return env, storage, (lambda obs: col.collect()), (actor, critic, col)
+        normalizers = None
+        if norm:
+            from robot_lab_amd.obsnorm import ObsNormalizer  # noqa: E402
+
+            normalizers = (ObsNormalizer(od, max_rows=N, device="cuda:0"), ObsNormalizer(cd, max_rows=N, device="cuda:0"))
+        col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, overlap=OVERLAP, critic_small=SMALL, fused_act=fused_act, normalizers=normalizers)
+        return env, storage, (lambda obs: col.collect()), (actor, critic, col, normalizers)
+    if norm:
+        raise SystemExit("--obs-normalization measures the captured loop: leave RL_GRAPH, RL_FUSED_RECORD and RL_PAIR at 1")
 
     def iteration(obs):
         storage.clear()
@@ -115,6 +127,37 @@ if ap_hist > 0:
         print(f"{task} N={N} {what}: history {ap_hist} costs {on - off:+.2f} us/step ({100 * (on - off) / off:+.1f} %) over history off (medians of {ROUNDS} alternating windows)")
     ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values())
     print(f"finite: {ok}")
+    sys.exit(0 if ok else 1)
+
+if ap_norm:
+    # fused-act loop (the default), the unfused loop (actor + critic, act kernel) and the normalised loop (apply_pair, actor + critic, act kernel,
+    # env step, update_pair), alternating steady-state windows in ONE process: us per step of the collection loop, every window listed
+    ROUNDS = 6
+    kinds = {"fused_act": dict(norm=False, fused_act=True), "unfused_act": dict(norm=False, fused_act=False), "normalized": dict(norm=True)}
+    sides = {}
+    with torch.inference_mode():
+        for name, kw in kinds.items():
+            env, storage, iteration, keep = setup(0, **kw)
+            obs = env.get_observations()
+            for _ in range(3):
+                obs = iteration(obs)
+            sides[name] = dict(env=env, storage=storage, iteration=iteration, keep=keep, obs=obs, collect=[])
+        order = list(kinds)
+        for r in range(ROUNDS):
+            for name in (order if r % 2 == 0 else order[::-1]):
+                sd = sides[name]
+                dt, sd["obs"] = window(sd["iteration"], sd["obs"], ITERS)
+                sd["collect"].append(1e6 * dt / ITERS / T)
+    for name, sd in sides.items():
+        v = np.array(sd["collect"])
+        print(f"{task} N={N} {name:12s} collect us/step: windows {np.round(v, 2).tolist()} median {np.median(v):.2f} min {v.min():.2f} max {v.max():.2f}")
+    med = {name: float(np.median(sd["collect"])) for name, sd in sides.items()}
+    print(f"{task} N={N}: normalisation costs {med['normalized'] - med['fused_act']:+.2f} us/step ({100 * (med['normalized'] - med['fused_act']) / med['fused_act']:+.1f} %) over the "
+          f"fused-act loop: {med['unfused_act'] - med['fused_act']:+.2f} for the act kernel as a launch of its own, {med['normalized'] - med['unfused_act']:+.2f} for apply_pair + update_pair "
+          f"(medians of {ROUNDS} alternating windows)")
+    count = int(sides["normalized"]["keep"][3][0].get_state()[3])
+    ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values()) and count > 0
+    print(f"finite: {ok}; rows seen by the policy group's statistics: {count}")
     sys.exit(0 if ok else 1)
 
 env, storage, iteration, _keep = setup(0)

@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--mirror-loss", type=float, default=None, metavar="C", help="coefficient of the mirror loss on the --symmetry tables (default: off)")
     ap.add_argument("--no-data-augmentation", action="store_true", help="with --mirror-loss: the PPO terms stay on the stored rows")
     ap.add_argument("--obs-history", type=int, default=0, metavar="N", help="policy-group observation history of N frames (IsaacLab's ObservationGroupCfg.history_length)")
+    ap.add_argument("--obs-normalization", action="store_true", help="rsl_rl's empirical normalisation of both observation groups (actor_obs_normalization, critic_obs_normalization)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--also-terminate-on", default="", help="DIAGNOSTIC, not the reference's cfg: regex of body names added to the illegal-contact termination")
@@ -61,7 +62,8 @@ def main():
         env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=a.seed, device="cuda:0", obs_history=hist)
     print(env, flush=True)  # (names the step kernel: specialised on the task, or the interpreter)
     mirror = dict(mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation) if a.symmetry else {}
-    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror)
+    norm = dict(actor_obs_normalization=True, critic_obs_normalization=True) if a.obs_normalization else {}
+    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror, **norm)
     print(tr, flush=True)
     # init_at_random_ep_len=True (train.py:224): the first time-outs are spread over an episode length
     env.episode_length_buf = torch.randint(0, env.max_episode_length, (a.num_envs,), generator=torch.Generator().manual_seed(a.seed))
@@ -77,7 +79,7 @@ def main():
         t1 = time.perf_counter()
         st = tr.storage
         row = dict(iteration=it, mean_step_reward=float(st.rewards.mean()), done_rate=float(st.dones.float().mean()))
-        row.update(tr.alg.update(st, tr.gen))
+        row.update(tr.alg.update(tr.update_batch(), tr.gen))
         tr.push_parameters()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
@@ -101,7 +103,7 @@ def main():
                   f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
     wall = time.perf_counter() - t_start
     n_steps = a.iterations * st.num_transitions_per_env * a.num_envs
-    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
+    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
                    collect_ms_per_iteration=1e3 * t_collect / a.iterations, update_ms_per_iteration=1e3 * t_update / a.iterations,
                    first=log[0], last=log[-1])
     print(json.dumps({k: v for k, v in summary.items() if k not in ("first", "last")}))
