@@ -12,6 +12,8 @@
  * (no floating-point atomics): the same state and permutation give bit-identical parameters.
  * Symmetry: rl_ppo_set_symmetry (data augmentation) and, on its tables, rl_ppo_set_mirror_loss (rsl_rl's mirror loss, with or without
  * the augmentation); a handle on which neither was called launches the kernels of a learner without them.
+ * Observation normalisation: rl_ppo_set_obs_normalization - the batch holds raw rows and the first layer's operand fetch normalises them,
+ * behind the mirror, with the statistics the normalisers hold at launch time; never called: the kernels of a learner without it.
  * Several GPUs (rsl_rl's multi-GPU contract, robot_lab_amd/dist.py): rl_ppo_set_world, then per update rl_ppo_update_begin and per mini-batch
  * rl_ppo_minibatch_local -> the CALLER's SUM all-reduce of the wire (rl_ppo_wire: the flat gradient and the KL statistic in one buffer, so
  * one collective per mini-batch) -> rl_ppo_minibatch_apply.  The library holds no communicator; the split sequence only enqueues as well.
@@ -89,6 +91,21 @@ int rl_ppo_set_symmetry(rl_ppo* p, int32_t n_sym, const int32_t* obs_perm, const
  * reason: no symmetry set, n_sym < 2, a coefficient that is not finite or <= 0, after the first mini-batch, a second call.  Never called:
  * the kernels and the results of a learner without it, bit for bit. */
 int rl_ppo_set_mirror_loss(rl_ppo* p, float coeff, int32_t data_augmentation);
+
+/* Observation normalisation inside the update (rsl_rl's `actor_obs_normalization` / `critic_obs_normalization`; the rule is `PPO.update` of
+ * robot_lab_amd/ppo.py on RAW stored rows): the batch's observations / privileged_observations are raw, and the network input of copy s of a
+ * row o is y[c] = (x[c] - mean[c]) / (std[c] + eps) with x = S_s(o) the mirrored row (x = o without a symmetry) and the statistics of the
+ * DESTINATION column c - the mirrored raw row is normalised, as rsl_rl does, which is the mirror of the normalised row only for symmetric
+ * statistics.  Three fp32 roundings with a correctly rounded division: the bits of rl_obsnorm_apply (include/rl_obsnorm.h).  Fused into
+ * the operand fetch of the first layer's forward and dW GEMMs, behind the mirror: no normalised copy of the batch is written to memory.
+ * mean / std: DEVICE vectors of the group's input width (the buffers rl_obsnorm_state_pointers returns); a NULL / NULL pair = that group is
+ * not normalised.  The kernels read them at launch time in stream order - an rl_obsnorm_update enqueued before an update is seen by it - and
+ * the caller keeps them alive as long as the handle enqueues.  Actions, the mirror loss and the KL statistic are untouched.
+ * Called once, before the first rl_ppo_minibatch_grad / rl_ppo_update, in any order with rl_ppo_set_symmetry / rl_ppo_set_mirror_loss; no
+ * device work.  Refused with a reason, the handle as it was: a null handle, both pairs null, half a pair, an eps that is not finite or < 0,
+ * a second call, a call after the first mini-batch.  Never called: the kernels and the results of a learner without it, bit for bit. */
+int rl_ppo_set_obs_normalization(rl_ppo* p, const float* actor_mean_dev, const float* actor_std_dev, float actor_eps,
+                                 const float* critic_mean_dev, const float* critic_std_dev, float critic_eps);
 
 /* nn.Linear images ([out][in], [out]) per layer + std[act], device pointers; stream-ordered device-to-device copies.  A null array / pointer
  * skips that part.  set: also what a loaded checkpoint goes through; get: the way back into an `ActorCritic.state_dict()`. */

@@ -243,7 +243,7 @@ PPO_LIB = os.path.join(_HERE, "csrc", "librl_ppo_hip.so")
 PPO_EXPORTS = ["rl_ppo_create", "rl_ppo_destroy", "rl_ppo_last_error", "rl_ppo_num_parameters", "rl_ppo_set_parameters", "rl_ppo_get_parameters",
                "rl_ppo_parameter_pointers", "rl_ppo_get_flat", "rl_ppo_minibatch_grad", "rl_ppo_update", "rl_ppo_stats", "rl_ppo_set_symmetry",
                "rl_ppo_set_mirror_loss", "rl_ppo_stats_ex", "rl_ppo_set_world", "rl_ppo_wire", "rl_ppo_update_begin", "rl_ppo_minibatch_local",
-               "rl_ppo_minibatch_apply", "rl_ppo_set_flat", "rl_ppo_get_optimizer", "rl_ppo_set_optimizer"]
+               "rl_ppo_minibatch_apply", "rl_ppo_set_flat", "rl_ppo_get_optimizer", "rl_ppo_set_optimizer", "rl_ppo_set_obs_normalization"]
 _ppo_lib = None
 
 
@@ -296,6 +296,7 @@ def load_ppo_library(path: str | None = None) -> C.CDLL:
     lib.rl_ppo_set_flat.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.rl_ppo_get_optimizer.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p]
     lib.rl_ppo_set_optimizer.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_void_p]
+    lib.rl_ppo_set_obs_normalization.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_float]
     if path == PPO_LIB:
         _ppo_lib = lib
     return lib

@@ -17,6 +17,10 @@
 //             c dL_mirror / dmean to its own row of dmean; a fourth per-block partial carries sum (mu - tau)^2.  Without the augmentation
 //             only the ACTOR's problems keep n_sym n rows: the critic's problems, the std column sum and the loss means are those of the n
 //             stored rows, and a row of a copy >= 1 carries the mirror gradient alone
+//   obsnorm   (rl_ppo_set_obs_normalization) the batch holds RAW rows: the layer-0 forward and dW launches are the NORM instantiations of the GEMM, whose
+//             fetch of X (or, without SYM, its stash into LDS) puts every loaded element - after the mirror - through y = (x - mean[c]) / (std[c] + eps) with the statistics of the
+//             DESTINATION column c, rl_obsnorm_apply's three fp32 roundings; the statistics are read from the normalisers' own device vectors
+//             at launch time; a group without statistics passes through the same launch unnormalised; no normalised copy of the batch exists
 //   step      sum of squares in fixed blocks -> every block of the Adam kernel adds the same partials in the same order: norm, clip
 //             coefficient, Adam, floor of std
 //   world     (rl_ppo_set_world) one rank among several: rl_ppo_minibatch_local ends after the reduce launch and leaves the flat gradient and,
@@ -73,6 +77,29 @@ struct GemmBatch {
   GemmProb p[2 * RL_PPO_MAX_LAYERS];
 };
 
+// NORM: the statistics of the two observation groups, a second kernel argument of the NORM instantiations alone (GemmProb and the argument list of
+// every other instantiation stay what they were); indexed like GemmBatch::p, a null mean = the problem's X is not normalised
+struct NormProb {
+  const float* mean;
+  const float* std;
+  float eps;
+};
+struct NormBatch {
+  NormProb p[2 * RL_PPO_MAX_LAYERS];
+};
+// rl_obsnorm_apply's expression (csrc/rl_obsnorm.hip), bit for bit: an addition, a subtraction and a correctly rounded division in fp32, never fused
+// and never a multiplication by a reciprocal.  The divisor of a column is formed once and kept
+__device__ __forceinline__ float norm_divisor(float std, float eps) {
+#pragma clang fp contract(off)
+  return std + eps;
+}
+__device__ __forceinline__ float norm_apply(float x, float mean, float divisor) {
+#pragma clang fp contract(off)
+  return (x - mean) / divisor;
+}
+__device__ __forceinline__ const NormProb* norm_prob(int) { return nullptr; }
+__device__ __forceinline__ const NormProb* norm_prob(int z, const NormBatch& nb) { return &nb.p[z]; }
+
 // a symmetry table word: the source column, and the sign in the float's sign position (the mirror is an exact XOR)
 constexpr int SYM_COL = 0x7fffffff, SYM_NEG = (int)0x80000000u;
 __device__ __forceinline__ float sym_read(const float* row, int word) {
@@ -80,9 +107,14 @@ __device__ __forceinline__ float sym_read(const float* row, int word) {
 }
 
 // SYM (G_FWD, G_DW of a layer-0 launch): X is read through the symmetry tables, see GemmProb::sym.  SYM = false is the plain gather.
-template <int MODE, bool SYM>
-__global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
+// NORM (G_FWD, G_DW of a layer-0 launch of a handle with rl_ppo_set_obs_normalization): the pack holds one NormBatch and every loaded element of X
+// goes through norm_apply after the mirror; elements outside the problem stay 0.  An empty pack is the kernel of a learner without it, argument
+// list included.
+template <int MODE, bool SYM, class... NORM>
+__global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch, NORM... norm) {
   static_assert(!SYM || MODE != G_DX, "only the operands that read X are mirrored");
+  constexpr bool NRM = sizeof...(NORM) != 0;
+  static_assert(!NRM || MODE != G_DX, "only the operands that read X are normalised");
   const GemmProb& P = batch.p[blockIdx.z];
   if ((int)blockIdx.x >= P.ntiles || (int)blockIdx.y >= (MODE == G_DW ? P.S : 1)) return;  // (uniform for the workgroup)
   __shared__ float As[TK * LD];
@@ -112,6 +144,16 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
     }
   }
   const bool b_sym = SYM && MODE == G_DW && P.sym != nullptr;  // (uniform for the workgroup)
+  const NormProb* NP = norm_prob((int)blockIdx.z, norm...);
+  const bool normed = NRM && NP->mean != nullptr;            // (uniform for the workgroup)
+  // (NORM, G_DW) a thread's column j0 + b_o of X is fixed for the whole kernel: its statistics are loaded once
+  float b_mean = 0.f, b_div = 1.f;
+  if constexpr (NRM && MODE == G_DW) {
+    if (normed && j0 + b_o < P.J) {
+      b_mean = NP->mean[j0 + b_o];
+      b_div = norm_divisor(NP->std[j0 + b_o], NP->eps);
+    }
+  }
   if (B_RC) {
     for (int p = 0; p < 8; ++p) {
       const int j = j0 + b_o + 16 * p;
@@ -119,11 +161,35 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
     }
   }
   float ra[8], rb[8];
+  // (NORM) fetch loads the slice's elements and, G_FWD, the statistics of its column r0 + a_r (a thread's eight elements share it: one pair of loads
+  // per slice, issued with the slice's own).  WHERE the divisions run is measured (profiles/ppo_hip_obsnorm_in_learner.txt): without SYM in stash, on
+  // the way into LDS - after the multiply loop that the loads travel under, not in front of it, where they would wait for the loads (an update
+  // with both groups normalised: +4 % instead of +13 %); with SYM in fetch - its dependent table-word and element loads are waited for there anyway, and
+  // the later form costs registers (+2.8 % instead of +5.2 %)
+  constexpr bool LATE = !SYM;
+  float a_mean = 0.f, a_div = 1.f;
+  int f_r0 = 0;  // the slice `ra` / `rb` hold
+  // (NORM) element p of the held slice - of ra (G_FWD) or rb (G_DW) - in place, if it lies `inside` the problem: an element outside stays 0, never
+  // (0 - mean) / divisor.  Called from fetch, where the load's own predicate says `inside`, or from stash, see LATE
+  auto normalise = [&](int p, bool inside) {
+    if constexpr (NRM) {
+      if (!normed || !inside) return;
+      if (MODE == G_FWD) ra[p] = norm_apply(ra[p], a_mean, a_div);
+      else rb[p] = norm_apply(rb[p], b_mean, b_div);
+    }
+  };
   auto fetch = [&](int r0) {
     int sv = 0, mv = 0;  // (SYM, G_DW) copy and stored-row slot of the virtual row r0 + b_r + 2 p
     if (b_sym) {
       sv = (r0 + b_r) / P.n0;
       mv = (r0 + b_r) - sv * P.n0;
+    }
+    if constexpr (NRM && LATE) f_r0 = r0;
+    if constexpr (NRM && MODE == G_FWD) {
+      if (normed && r0 + a_r < r_end) {
+        a_mean = NP->mean[r0 + a_r];
+        a_div = norm_divisor(NP->std[r0 + a_r], NP->eps);
+      }
     }
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
@@ -131,6 +197,7 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
         const int i = i0 + a_o + 16 * p, r = r0 + a_r;
         if (SYM && MODE == G_FWD) ra[p] = (i < P.I && r < r_end) ? sym_read(P.A + a_row[p], P.sym[a_tab[p] + r]) : 0.f;
         else ra[p] = (i < P.I && r < r_end) ? P.A[a_row[p] + r] : 0.f;
+        if constexpr (NRM && MODE == G_FWD && !LATE) normalise(p, i < P.I && r < r_end);
       } else {
         const int i = i0 + a_o, r = r0 + a_r + 2 * p;
         ra[p] = (i < P.I && r < r_end) ? P.A[(size_t)r * P.lda + i] : 0.f;
@@ -149,12 +216,15 @@ __global__ __launch_bounds__(256, 2) void ppo_gemm_kernel(GemmBatch batch) {
           v = P.B[row * P.ldb + j];
         }
         rb[p] = v;
+        if constexpr (NRM && MODE == G_DW && !LATE) normalise(p, j < P.J && r < r_end);
       }
     }
   };
   auto stash = [&]() {
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
+      if constexpr (NRM && LATE)
+        normalise(p, MODE == G_FWD ? i0 + a_o + 16 * p < P.I && f_r0 + a_r < r_end : j0 + b_o < P.J && f_r0 + b_r + 2 * p < r_end);
       if (A_RC) As[a_r * LD + a_o + 16 * p] = ra[p];
       else As[(a_r + 2 * p) * LD + a_o] = ra[p];
       if (B_RC) Bs[b_r * LD + b_o + 16 * p] = rb[p];
@@ -532,6 +602,8 @@ struct rl_ppo {
   float mirror = 0.f;             // coefficient of the mirror loss; 0: rl_ppo_set_mirror_loss was not called
   bool augment = true;            // (mirror loss) the PPO terms see every copy; false: the stored rows only
   double* mirror_part = nullptr;  // the head's fourth partials
+  bool norm = false;              // rl_ppo_set_obs_normalization was called: the batch holds raw rows, the layer-0 launches are the NORM kernels
+  NormProb norm_of[2] = {};       // the caller's statistics of the actor's / the critic's input (a null mean: that group is not normalised)
   int world = 0;                  // ranks whose gradients the caller sums into the wire; 0: rl_ppo_set_world was not called (one rank)
   bool local_pending = false;     // rl_ppo_minibatch_local ran and rl_ppo_minibatch_apply has not yet
 };
@@ -597,6 +669,9 @@ template <class K>
 K* side(bool flag, K* on, K* off) {
   return flag ? on : off;
 }
+// the two argument lists of ppo_gemm_kernel (side<GemmK>(...) picks the instantiation with the empty NORM pack)
+using GemmK = void(GemmBatch);
+using GemmNormK = void(GemmBatch, NormBatch);
 
 // sum of squares -> clip -> Adam -> floor of std on the flat gradient; with a world > 1 on g[i] / world (the wire holds the ranks' SUM)
 void optimiser_step(rl_ppo* p, hipStream_t s) {
@@ -652,7 +727,13 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
       gemm_prob(gb.p[k], p, b, idx, n0, G_FWD, k, l, rows_of[k]);
       tiles = std::max(tiles, gb.p[k].ntiles);
     }
-    hipLaunchKernelGGL(side(sym && l == 0, ppo_gemm_kernel<G_FWD, true>, ppo_gemm_kernel<G_FWD, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+    if (p->norm && l == 0) {
+      NormBatch nb{};
+      nb.p[0] = p->norm_of[0]; nb.p[1] = p->norm_of[1];
+      hipLaunchKernelGGL(side<GemmNormK>(sym, ppo_gemm_kernel<G_FWD, true>, ppo_gemm_kernel<G_FWD, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb, nb);
+    } else {
+      hipLaunchKernelGGL(side<GemmK>(sym && l == 0, ppo_gemm_kernel<G_FWD, true>, ppo_gemm_kernel<G_FWD, false>), dim3(tiles, 1, 2), dim3(256), 0, s, gb);
+    }
   }
   {
     HeadArgs a{};
@@ -704,7 +785,13 @@ int minibatch(rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int 
     RedProb& r = rb.p[np];
     r.part = p->std_part; r.out = p->grads; r.count = p->A; r.stride = p->A; r.S = p->S_std;
     colx = std::max(colx, (p->A + 63) / 64); Smax = std::max(Smax, p->S_std);
-    hipLaunchKernelGGL(side(sym, ppo_gemm_kernel<G_DW, true>, ppo_gemm_kernel<G_DW, false>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
+    if (p->norm) {
+      NormBatch nb{};  // (problem k L + l: the layer-0 problems of the two networks carry the statistics)
+      nb.p[0] = p->norm_of[0]; nb.p[L] = p->norm_of[1];
+      hipLaunchKernelGGL(side<GemmNormK>(sym, ppo_gemm_kernel<G_DW, true>, ppo_gemm_kernel<G_DW, false>), dim3(tiles, Smax, np), dim3(256), 0, s, gb, nb);
+    } else {
+      hipLaunchKernelGGL(side<GemmK>(sym, ppo_gemm_kernel<G_DW, true>, ppo_gemm_kernel<G_DW, false>), dim3(tiles, Smax, np), dim3(256), 0, s, gb);
+    }
     hipLaunchKernelGGL(ppo_colsum_kernel, dim3(colx, Smax, np + 1), dim3(256), 0, s, cb);
     hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)std::min<long>((redmax + 255) / 256, 512), np + 1), dim3(256), 0, s, rb);
   }
@@ -887,6 +974,31 @@ int rl_ppo_set_mirror_loss(rl_ppo* p, float coeff, int32_t data_augmentation) {
   if (!std::isfinite(coeff) || !(coeff > 0.f)) return fail("rl_ppo_set_mirror_loss: the coefficient must be finite and > 0, got " + std::to_string(coeff));
   p->mirror = coeff;  // (no device work: the fourth partials are allocated with the other mini-batch buffers)
   p->augment = data_augmentation != 0;
+  return 0;
+}
+
+int rl_ppo_set_obs_normalization(rl_ppo* p, const float* actor_mean_dev, const float* actor_std_dev, float actor_eps, const float* critic_mean_dev,
+                                 const float* critic_std_dev, float critic_eps) {
+  if (!p) return fail("null argument");
+  if (p->norm)
+    return fail("rl_ppo_set_obs_normalization: the observation normalisation of this learner is already set (it is set once, before the first mini-batch)");
+  if (p->started)
+    return fail("rl_ppo_set_obs_normalization: refused after the first rl_ppo_minibatch_grad / rl_ppo_update - the mini-batches before it read the "
+                "batch unnormalised; create a new learner");
+  const char* names[2] = {"actor", "critic"};
+  const float* mean[2] = {actor_mean_dev, critic_mean_dev};
+  const float* sd[2] = {actor_std_dev, critic_std_dev};
+  const float eps[2] = {actor_eps, critic_eps};
+  if (!mean[0] && !sd[0] && !mean[1] && !sd[1])
+    return fail("rl_ppo_set_obs_normalization: both groups are null - a learner without normalisation is one on which this is not called");
+  for (int k = 0; k < 2; ++k) {
+    if ((mean[k] == nullptr) != (sd[k] == nullptr))
+      return fail(std::string("rl_ppo_set_obs_normalization: ") + names[k] + " mean and std are both given or both null");
+    if (mean[k] && (!std::isfinite(eps[k]) || !(eps[k] >= 0.f)))
+      return fail(std::string("rl_ppo_set_obs_normalization: the ") + names[k] + " eps must be finite and >= 0, got " + std::to_string(eps[k]));
+  }
+  for (int k = 0; k < 2; ++k) p->norm_of[k] = NormProb{mean[k], sd[k], mean[k] ? eps[k] : 0.f};  // (no device work: the kernels read the vectors at launch time)
+  p->norm = true;
   return 0;
 }
 

@@ -122,6 +122,11 @@ class ObsNormalizer:
                                                    other._rows(other_out, "out"), x.shape[0], self._stream()))
         return out, other_out
 
+    def device_pointers(self):
+        """(address of mean, address of std, eps): what a kernel that normalises for itself reads (`rl_ppo_set_obs_normalization`).  The
+        addresses are fixed for the life of the handle; whoever keeps them keeps a reference to this object."""
+        return self.mean.data_ptr(), self.std.data_ptr(), self.eps
+
     # -- state --------------------------------------------------------------------------------------------------------------------
     def set_state(self, mean, var, std, count: int):
         """the three vectors (fp32 device tensors of dim entries, any shape) and the count, stream-ordered (`rl_obsnorm_set_state`)"""

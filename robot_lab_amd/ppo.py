@@ -306,12 +306,16 @@ class Trainer:
     `actor_obs_normalization`, `critic_obs_normalization`: rsl_rl's empirical normalisation of the group (`EmpiricalNormalization` is the
     rule, csrc/rl_obsnorm.hip runs it): statistics updated inside the captured collection loop with the NEW observations of every step,
     applied in front of both networks there, and once per update over the stored RAW rows with the statistics as the collection left
-    them.  `state_dict()` gains rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` keys.  Refused with `symmetry` and with a
-    `group` of more than one rank."""
+    them.  `state_dict()` gains rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` keys.  Refused with a `group` of more than
+    one rank, and - unless `normalize_in_learner` - with `symmetry`.
+    `normalize_in_learner=True` (with a normalisation flag): the update reads the RAW storage and the learner normalises - the torch learner
+    through the modules' forward, the HIP learner in its first layer's operand fetch (`HipPPO(obs_normalizers=...)`), both behind the mirror, as
+    rsl_rl does: the mirrored raw row is normalised.  No normalised copy of the batch is allocated.  This is what `symmetry` / `mirror_loss`
+    need together with normalised observations; the default stays the scratch matrices of `NormalizedBatch`."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
                  critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None,
-                 actor_obs_normalization=False, critic_obs_normalization=False, **ppo_kw):
+                 actor_obs_normalization=False, critic_obs_normalization=False, normalize_in_learner=False, **ppo_kw):
         from .collect import Collector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
@@ -325,10 +329,14 @@ class Trainer:
                                  f", the fused inference kernels and the HIP learner take at most {MAX_INPUT_WIDTH} input columns: shorten the "
                                  f"{name} group's history_length or drop terms from it")
         normalized = tuple(name for name, on in (("policy", actor_obs_normalization), ("critic", critic_obs_normalization)) if on)
-        if normalized and symmetry is not None:
-            raise NotImplementedError("Trainer: symmetry= together with observation normalisation is not implemented: rsl_rl normalises the MIRRORED raw row, "
-                                      "which is not the mirror of the normalised row unless the statistics are symmetric, and the learners mirror inside "
-                                      "their first layer's operand fetch, behind the normalisation (drop symmetry=, or the *_obs_normalization flags)")
+        normalize_in_learner = bool(normalize_in_learner)
+        if normalize_in_learner and not normalized:
+            raise ValueError("Trainer: normalize_in_learner=True without actor_obs_normalization / critic_obs_normalization: there is nothing to normalise")
+        if normalized and symmetry is not None and not normalize_in_learner:
+            raise NotImplementedError("Trainer: symmetry= together with observation normalisation needs normalize_in_learner=True: rsl_rl normalises the "
+                                      "MIRRORED raw row, which is not the mirror of the normalised row unless the statistics are symmetric, and by default "
+                                      "the learners read a batch that was normalised before their first layer's operand fetch mirrors it "
+                                      "(pass normalize_in_learner=True, or drop symmetry= or the *_obs_normalization flags)")
         if normalized and group is not None and getattr(group, "world_size", 1) > 1:
             raise NotImplementedError(f"Trainer: observation normalisation with a group of {group.world_size} ranks is not implemented: whether the ranks "
                                       "keep their own statistics or reduce them is not decided here (run one rank, or drop the *_obs_normalization flags)")
@@ -339,7 +347,7 @@ class Trainer:
                                       bool(critic_obs_normalization)).to(self.device)
         else:
             self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std).to(self.device)
-        self.normalized = normalized
+        self.normalized, self.normalize_in_learner = normalized, normalize_in_learner
         if learner not in ("torch", "hip"):
             raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
         self.learner = learner
@@ -354,6 +362,15 @@ class Trainer:
                 symmetry = tables_for_env(env, symmetry)
             ppo_kw["symmetry"] = symmetry
         self.symmetry = symmetry
+        self.normalizers = None
+        if normalized:  # the device half of the policy's EmpiricalNormalization modules
+            from .obsnorm import ObsNormalizer
+
+            mods = (self.policy.actor_obs_normalizer, self.policy.critic_obs_normalizer)
+            self.normalizers = tuple(ObsNormalizer(m._mean.shape[1], m.eps, max_rows=env.num_envs, device=str(self.device)) if isinstance(m, EmpiricalNormalization)
+                                     else None for m in mods)
+            if normalize_in_learner and learner == "hip":
+                ppo_kw["obs_normalizers"] = self.normalizers  # (the torch learner runs the modules' forward on the raw batch)
         if learner == "hip":
             from .ppo_hip import HipPPO
 
@@ -370,14 +387,10 @@ class Trainer:
         self.critic = MlpPolicy([host(x.weight) for x in lin(self.policy.critic)], [host(x.bias) for x in lin(self.policy.critic)], "elu", device=str(self.device))
         self.storage = RolloutStorage(env.num_envs, num_steps_per_env, od, cd, A, seed=seed, device=str(self.device))
         self.std = self.policy.std.detach().clone()  # the tensor the sampling kernel reads: refreshed in place after every update
-        self.normalizers, self._batch = None, self.storage
-        if normalized:  # the device half of the policy's EmpiricalNormalization modules + the update's normalised [T N, dim] matrices
-            from .obsnorm import ObsNormalizer
-
-            mods = (self.policy.actor_obs_normalizer, self.policy.critic_obs_normalizer)
-            self.normalizers = tuple(ObsNormalizer(m._mean.shape[1], m.eps, max_rows=env.num_envs, device=str(self.device)) if isinstance(m, EmpiricalNormalization)
-                                     else None for m in mods)
-            self._batch = NormalizedBatch(self.storage, self.normalizers)
+        self._batch = self.storage
+        if normalized:
+            if not normalize_in_learner:  # the update's normalised [T N, dim] matrices
+                self._batch = NormalizedBatch(self.storage, self.normalizers)
             self.collector = Collector(env, self.actor, self.critic, self.storage, self.std, gamma=gamma, lam=lam, use_graph=use_graph, clip_actions=clip_actions,
                                        normalizers=self.normalizers)
         else:
@@ -388,6 +401,7 @@ class Trainer:
     def __repr__(self):
         sym = f", symmetry={self.symmetry!r}{mirror_repr(self.alg)}" if self.symmetry is not None else ""
         sym += f", obs_normalization={list(self.normalized)}" if self.normalized else ""
+        sym += ", normalize_in_learner=True" if self.normalize_in_learner else ""
         return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration}{sym})"
 
     def _modules(self):
@@ -427,11 +441,15 @@ class Trainer:
         self.std.copy_(self.policy.std.detach().clamp_min(1e-6))
 
     def update_batch(self):
-        """the filled storage as the learner reads it: the storage itself, or - with observation normalisation - a `NormalizedBatch` whose two
-        observation matrices hold the stored raw rows through the statistics as the collection left them (one `apply` per group)"""
+        """the filled storage as the learner reads it: the storage itself (no normalisation, or `normalize_in_learner`: the learner normalises the
+        raw rows), or - with observation normalisation - a `NormalizedBatch` whose two observation matrices hold the stored raw rows through the
+        statistics as the collection left them (one `apply` per group)"""
         if self.normalized:
-            self._batch.normalize()
-            self.sync_normalizers()  # (`alg.policy`'s buffers stay current: the torch rule, exporters and checkpoints read them)
+            if not self.normalize_in_learner:
+                self._batch.normalize()
+            # `alg.policy`'s buffers stay current: the torch rule (with `normalize_in_learner` its forward over the raw batch), exporters and
+            # checkpoints read them; the HIP learner reads the handles' own vectors
+            self.sync_normalizers()
         return self._batch
 
     def iterate(self) -> dict:

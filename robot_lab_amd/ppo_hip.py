@@ -17,6 +17,12 @@ fused into the first layer's operand fetch and the loss head (`rl_ppo_set_symmet
 `HipPPO(policy, symmetry=tables, mirror_loss=c, data_augmentation=True | False)`: rsl_rl's mirror loss on the same tables, as `ppo.PPO`
 defines it (`rl_ppo_set_mirror_loss`); `update()` then returns `mirror_loss` too, read in the same one wait (`rl_ppo_stats_ex`).
 
+`HipPPO(policy, obs_normalizers=(actor | None, critic | None))` (`obsnorm.ObsNormalizer` handles, the device half of the policy's
+`actor_obs_normalizer` / `critic_obs_normalizer`): the storage given to `update()` holds RAW rows and the first layer's operand fetch
+normalises them - behind the mirror, with the statistics the handles hold when the kernels run (`rl_ppo_set_obs_normalization`): the rule of
+`ppo.PPO.update` on a raw batch, and what makes `symmetry=` and normalised observations go together.  Without the keyword a policy with
+normalisers is fed matrices that were normalised before (`ppo.NormalizedBatch`).
+
 `HipPPO(policy, group=g)` (a `dist.LearnerGroup`, or anything with `world_size`, `enabled` and an in-place `all_reduce_sum(tensor)`): rsl_rl's
 multi-GPU contract.  The library holds no communicator: with an enabled group `update()` runs `rl_ppo_update_begin`, then per mini-batch
 `rl_ppo_minibatch_local` -> `group.all_reduce_sum(wire)` -> `rl_ppo_minibatch_apply`, all on the current stream, and reads the one statistics
@@ -123,7 +129,8 @@ class HipPPO:
 
     def __init__(self, policy, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01, num_learning_epochs=5,
                  num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0, group=None,
-                 max_rows_per_minibatch=None, lib_path: str | None = None, symmetry=None, mirror_loss=None, data_augmentation=True):
+                 max_rows_per_minibatch=None, lib_path: str | None = None, symmetry=None, mirror_loss=None, data_augmentation=True,
+                 obs_normalizers=None):
         import torch
 
         from .ppo import check_mirror_loss
@@ -163,6 +170,7 @@ class HipPPO:
                 raise TypeError(f"HipPPO: symmetry must be a robot_lab_amd.symmetry.SymmetryTables (or None), not {type(symmetry).__name__}")
             symmetry.check_widths(adims[0], cdims[0], adims[-1])
         self.symmetry = symmetry
+        self.obs_normalizers = self._check_normalizers(policy, obs_normalizers, (adims[0], cdims[0]), std.device)  # (kept: the kernels read their memory)
         self._mirror = check_mirror_loss("HipPPO", symmetry, mirror_loss, data_augmentation)  # what the handle is given at its creation
         self.mirror_loss, self.data_augmentation = None, True  # what the handle HAS (set_mirror_loss)
         self.lib = load_ppo_library(lib_path)
@@ -206,10 +214,12 @@ class HipPPO:
                 self.set_symmetry(self.symmetry)
                 if self._mirror[0] is not None:
                     self.set_mirror_loss(*self._mirror)
+            if self.obs_normalizers is not None:
+                self._set_obs_normalization(self.obs_normalizers)
             if self.group is not None:
                 self._set_world(self.group.world_size)
         except Exception:
-            self.close()  # never a learner that quietly runs without the symmetry or the world it was asked for
+            self.close()  # never a learner that quietly runs without the symmetry, the normalisation or the world it was asked for
             raise
         self.num_parameters = int(self.lib.rl_ppo_num_parameters(self.handle))
         if self._opt_pending is not None:
@@ -244,6 +254,42 @@ class HipPPO:
             raise RlPpoError("HipPPO.set_mirror_loss before the handle exists: pass mirror_loss= to the constructor")
         self._check(self.lib.rl_ppo_set_mirror_loss(self.handle, float(coeff), int(bool(data_augmentation))))
         self.mirror_loss, self.data_augmentation = float(coeff), bool(data_augmentation)
+
+    @staticmethod
+    def _check_normalizers(policy, handles, widths, device):
+        """`obs_normalizers=` as a pair (actor handle | None, critic handle | None), or None; a ValueError says why a pair does not fit"""
+        if handles is None:
+            return None
+        from torch import nn
+
+        handles = tuple(handles)
+        if len(handles) != 2 or all(h is None for h in handles):
+            raise ValueError("HipPPO: obs_normalizers must be a pair (actor handle | None, critic handle | None) with at least one handle "
+                             "(no normalisation in the learner: drop the keyword)")
+        for name, h, width in zip(("actor", "critic"), handles, widths):
+            module = getattr(policy, f"{name}_obs_normalizer", None)
+            identity = module is None or isinstance(module, nn.Identity)
+            if h is None:
+                if not identity:
+                    raise ValueError(f"HipPPO: obs_normalizers has no handle for the {name}, but the policy's {name}_obs_normalizer is a "
+                                     f"{type(module).__name__}: the learner would train on raw rows a policy that normalises them")
+                continue
+            if identity:
+                raise ValueError(f"HipPPO: obs_normalizers has a handle for the {name}, but the policy's {name}_obs_normalizer is nn.Identity: the "
+                                 f"policy was built without {name}_obs_normalization")
+            if int(h.dim) != width:
+                raise ValueError(f"HipPPO: the {name}'s normaliser is {h.dim} columns wide, the network's input {width}")
+            if (h.device.type, h.device.index or 0) != (device.type, device.index or 0):  # ("cuda" is cuda:0, as obsnorm.py creates it)
+                raise ValueError(f"HipPPO: the {name}'s normaliser lives on {h.device}, the policy on {device}")
+        return handles
+
+    def _set_obs_normalization(self, handles):
+        """`rl_ppo_set_obs_normalization`: once per handle, before its first mini-batch (the constructor's `obs_normalizers=` at handle creation)"""
+        args = []
+        for h in handles:
+            mean, std, eps = h.device_pointers() if h is not None else (None, None, 0.0)
+            args += [C.c_void_p(mean), C.c_void_p(std), float(eps)]
+        self._check(self.lib.rl_ppo_set_obs_normalization(self.handle, *args))
 
     def _set_world(self, world_size):
         """`rl_ppo_set_world` + the wire adopted as a torch tensor (P + 1 floats of the learner's gradient buffer, no copy)"""
@@ -443,4 +489,6 @@ class HipPPO:
         from .ppo import mirror_repr
 
         sym = f", symmetry={self.symmetry!r}{mirror_repr(self)}" if self.symmetry is not None else ""
+        if self.obs_normalizers is not None:
+            sym += f", obs_normalizers={[n for n, h in zip(('actor', 'critic'), self.obs_normalizers) if h is not None]}"
         return f"HipPPO(actor={self.actor_dims}, critic={self.critic_dims}, schedule={self.schedule!r}, lr={self.learning_rate:g}{sym}, librl_ppo_hip)"

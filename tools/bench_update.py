@@ -23,7 +23,13 @@ loss with coefficient C, the mirror loss alone (`data_augmentation=False`: only 
 host-driven rl_ppo_update_begin / rl_ppo_minibatch_local / rl_ppo_minibatch_apply sequence of a multi-GPU run without the collective, beside the
 fused `rl_ppo_update` ("hip").  `split_over_fused` is what the split itself costs: one more small launch per mini-batch and a host that
 issues every mini-batch through Python instead of running ahead inside one library call.
-    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...] [--mirror-loss C] [--split]"""
+`--obs-normalization scratch|learner`: both observation groups normalised (`Trainer(actor_obs_normalization=True, critic_obs_normalization=True)`).
+"scratch": every timed update starts with the normalisation pass over the stored rows (`NormalizedBatch.normalize`, inside the window) and the
+learners read its matrices; "learner" (`normalize_in_learner=True`): the learners read the raw storage - torch through the modules' forward, HIP
+in its first layer's operand fetch (`HipPPO(obs_normalizers=...)`).  "scratch" is timed with symmetry "off" only: mirroring rows that were
+normalised before is not the rule, and the Trainer refuses it.
+    python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...] [--mirror-loss C] [--split]
+                                 [--obs-normalization scratch|learner]"""
 import argparse
 import copy
 import json
@@ -79,13 +85,17 @@ class WorldOfOne:
         return tensor
 
 
-def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_loss=None, split=False):
+def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_loss=None, split=False, obs_normalization=None):
     env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
-    tr = Trainer(env, seed=seed)
+    norm = dict(actor_obs_normalization=True, critic_obs_normalization=True, normalize_in_learner=obs_normalization == "learner") if obs_normalization else {}
+    tr = Trainer(env, seed=seed, **norm)
     tr.collector.collect()
     torch.cuda.synchronize()
     out, hip_off = [], None
     for spec in symmetry:
+        if obs_normalization == "scratch" and spec != "off":
+            print(f"# --obs-normalization scratch with symmetry {spec}: not timed (the mirror of a normalised row is not the rule; use learner)", file=sys.stderr, flush=True)
+            continue
         tab, kind = tables(env, spec, (tr.storage.observations.shape[-1], tr.storage.privileged_observations.shape[-1], env.num_actions))
         settings = [{}]  # keywords of both learners beside symmetry=
         if tab is not None and mirror_loss is not None:
@@ -93,6 +103,8 @@ def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_los
         for kw in settings:
             res = bench_one(tr, tab, repeat, warmup, seed, split=split, **kw)
             res = dict(task=task, num_envs=num_envs, symmetry=spec, tables=kind, n_sym=tab.n_sym if tab else 1, **res)
+            if obs_normalization:
+                res["obs_normalization"] = obs_normalization
             if mirror_loss is not None:
                 res.update(mirror_loss=kw.get("mirror_loss"), data_augmentation=kw.get("data_augmentation", True))
             if spec == "off":
@@ -108,9 +120,11 @@ def bench(task, num_envs, repeat, warmup, symmetry=("off",), seed=42, mirror_los
 
 def bench_one(tr, tab, repeat, warmup, seed, split=False, **kw):
     st = tr.storage
-    learners = {"torch": PPO(copy.deepcopy(tr.policy), symmetry=tab, **kw), "hip": HipPPO(copy.deepcopy(tr.policy), symmetry=tab, **kw)}
+    tr.sync_normalizers()  # (the modules the copied policies carry hold the collection's statistics)
+    hip_kw = dict(kw, obs_normalizers=tr.normalizers) if tr.normalize_in_learner else kw
+    learners = {"torch": PPO(copy.deepcopy(tr.policy), symmetry=tab, **kw), "hip": HipPPO(copy.deepcopy(tr.policy), symmetry=tab, **hip_kw)}
     if split:
-        learners["hip_split"] = HipPPO(copy.deepcopy(tr.policy), symmetry=tab, group=WorldOfOne(), **kw)
+        learners["hip_split"] = HipPPO(copy.deepcopy(tr.policy), symmetry=tab, group=WorldOfOne(), **hip_kw)
     gens = {k: torch.Generator(device="cuda:0").manual_seed(seed) for k in learners}
     times = {k: [] for k in learners}
     for it in range(warmup + repeat):
@@ -118,7 +132,7 @@ def bench_one(tr, tab, repeat, warmup, seed, split=False, **kw):
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             t0.record()
-            out = alg.update(st, gens[k])
+            out = alg.update(tr.update_batch(), gens[k])  # (with scratch normalisation: the pass over the stored rows is part of every update)
             t1.record()
             torch.cuda.synchronize()
             if it >= warmup:
@@ -147,6 +161,8 @@ def main():
     ap.add_argument("--symmetry", nargs="+", default=["off"], help="settings to time, each \"off\" or mirrors (lr | fb | lr,fb)")
     ap.add_argument("--mirror-loss", type=float, default=None, metavar="C", help="also time every symmetry setting with the mirror loss, with and without the augmentation")
     ap.add_argument("--split", action="store_true", help="also time the begin / local / apply sequence of a multi-GPU run at a world of one")
+    ap.add_argument("--obs-normalization", choices=("scratch", "learner"), default=None,
+                    help="normalise both observation groups: in a pass before every update (scratch) or inside the learners (learner)")
     a = ap.parse_args()
     for spec in a.symmetry:
         if spec != "off":
@@ -154,7 +170,7 @@ def main():
     if len(a.num_envs) != len(a.task):
         ap.error("one --num-envs per --task")
     for task, n in zip(a.task, a.num_envs):
-        for res in bench(task, n, a.repeat, a.warmup, a.symmetry, mirror_loss=a.mirror_loss, split=a.split):
+        for res in bench(task, n, a.repeat, a.warmup, a.symmetry, mirror_loss=a.mirror_loss, split=a.split, obs_normalization=a.obs_normalization):
             print(json.dumps(res), flush=True)
 
 

@@ -6,7 +6,9 @@
 Per kernel: the instruction lines between the kernel's label and its `.Lfunc_end` - comments, directives and the kernel descriptor dropped,
 the function number in basic-block labels (`.LBB<n>_`) normalised - are counted and hashed (sha1, first 12 hex digits) in both listings.
 Under a kernel: the descriptor fields (`.amdhsa_*`) that differ.  Kernels whose stream differs, and kernels only one side has, are listed with
-their VGPR / SGPR / LDS / scratch figures.  Streams are compared as text: no instruction is interpreted.  Exit status 1 if any stream differs."""
+their VGPR / SGPR / LDS / scratch figures.  Kernels are matched by their mangled symbol; a kernel that only one side has under its symbol is
+matched by its DEMANGLED name where exactly one kernel of either side carries it (a template that gained a defaulted or empty parameter keeps
+its demangled name and changes its symbol) and is marked "(by demangled name)".  Streams are compared as text: no instruction is interpreted.  Exit status 1 if any stream differs."""
 import hashlib
 import re
 import shutil
@@ -69,18 +71,24 @@ def main(parent_s, child_s):
     names = demangle(sorted(set(parent) | set(child)))
     print(f"{'kernel':<44}{'instr':>6}{'instr':>6}  {'sha1 parent':<13}{'sha1 child':<13}verdict")
     differ = 0
-    for n in sorted(set(parent) & set(child), key=names.get):
-        p, c = parent[n], child[n]
+    pairs = {n: n for n in set(parent) & set(child)}  # parent symbol -> child symbol
+    for s in {names[n] for n in parent if n not in child}:
+        ps, cs = [n for n in parent if n not in child and names[n] == s], [n for n in child if n not in parent and names[n] == s]
+        if len(ps) == 1 and len(cs) == 1:
+            pairs[ps[0]] = cs[0]
+    for n in sorted(pairs, key=names.get):
+        p, c = parent[n], child[pairs[n]]
         same = digest(p) == digest(c)
         differ += not same
-        print(f"{names[n]:<44}{len(p['stream']):>6}{len(c['stream']):>6}  {digest(p):<13}{digest(c):<13}{'identical' if same else 'DIFFERS'}")
+        print(f"{names[n]:<44}{len(p['stream']):>6}{len(c['stream']):>6}  {digest(p):<13}{digest(c):<13}{'identical' if same else 'DIFFERS'}" +
+              ("" if pairs[n] == n else "  (by demangled name)"))
         fields = {f: (p["desc"].get(f), c["desc"].get(f)) for f in sorted(set(p["desc"]) | set(c["desc"])) if p["desc"].get(f) != c["desc"].get(f)}
         if fields:
             print(f"    descriptor fields that differ: {fields}")
         if not same:
             print(f"    parent: {figures(p)}\n    child:  {figures(c)}")
-    for title, side, other in (("only in the parent", parent, child), ("new in the child", child, parent)):
-        only = sorted(set(side) - set(other), key=names.get)
+    for title, side, matched in (("only in the parent", parent, set(pairs)), ("new in the child", child, set(pairs.values()))):
+        only = sorted(set(side) - matched, key=names.get)
         if only:
             print(f"{title}:")
         for n in only:

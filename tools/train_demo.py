@@ -12,8 +12,10 @@ parity test against our own oracle can show.
 `--learner hip` runs the update as HIP kernels instead (robot_lab_amd/ppo_hip.py, csrc/rl_ppo.hip) and pushes with rl_mlp_set_weights_device.
 `--symmetry lr` (or `lr,fb`) turns on symmetry data augmentation inside the update of either learner (`Trainer(symmetry=...)`);
 `--mirror-loss C` adds rsl_rl's mirror loss with coefficient C on the same tables, `--no-data-augmentation` keeps the mirror loss alone.
+`--obs-normalization` normalises both observation groups; with `--normalize-in-learner` the learners read the raw storage and normalise for
+themselves (`Trainer(normalize_in_learner=True)`), which is what `--symmetry` / `--mirror-loss` need together with it.
     python tools/train_demo.py [--task ID] [--num-envs N] [--iterations K] [--learner torch|hip] [--symmetry lr|fb|lr,fb] [--mirror-loss C]
-                               [--no-data-augmentation] [--out DIR]"""
+                               [--no-data-augmentation] [--obs-normalization [--normalize-in-learner]] [--out DIR]"""
 import argparse
 import json
 import os
@@ -39,12 +41,16 @@ def main():
     ap.add_argument("--no-data-augmentation", action="store_true", help="with --mirror-loss: the PPO terms stay on the stored rows")
     ap.add_argument("--obs-history", type=int, default=0, metavar="N", help="policy-group observation history of N frames (IsaacLab's ObservationGroupCfg.history_length)")
     ap.add_argument("--obs-normalization", action="store_true", help="rsl_rl's empirical normalisation of both observation groups (actor_obs_normalization, critic_obs_normalization)")
+    ap.add_argument("--normalize-in-learner", action="store_true",
+                    help="with --obs-normalization: the learners normalise the raw stored rows themselves (needed together with --symmetry / --mirror-loss)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--also-terminate-on", default="", help="DIAGNOSTIC, not the reference's cfg: regex of body names added to the illegal-contact termination")
     a = ap.parse_args()
     if not a.symmetry and (a.mirror_loss is not None or a.no_data_augmentation):
         ap.error("--mirror-loss / --no-data-augmentation need --symmetry")
+    if a.normalize_in_learner and not a.obs_normalization:
+        ap.error("--normalize-in-learner needs --obs-normalization")
     hist = {"policy": a.obs_history} if a.obs_history else None
     if a.also_terminate_on:
         import re
@@ -62,7 +68,7 @@ def main():
         env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=a.seed, device="cuda:0", obs_history=hist)
     print(env, flush=True)  # (names the step kernel: specialised on the task, or the interpreter)
     mirror = dict(mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation) if a.symmetry else {}
-    norm = dict(actor_obs_normalization=True, critic_obs_normalization=True) if a.obs_normalization else {}
+    norm = dict(actor_obs_normalization=True, critic_obs_normalization=True, normalize_in_learner=a.normalize_in_learner) if a.obs_normalization else {}
     tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror, **norm)
     print(tr, flush=True)
     # init_at_random_ep_len=True (train.py:224): the first time-outs are spread over an episode length
@@ -103,7 +109,7 @@ def main():
                   f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
     wall = time.perf_counter() - t_start
     n_steps = a.iterations * st.num_transitions_per_env * a.num_envs
-    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
+    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), normalize_in_learner=bool(a.normalize_in_learner), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
                    collect_ms_per_iteration=1e3 * t_collect / a.iterations, update_ms_per_iteration=1e3 * t_update / a.iterations,
                    first=log[0], last=log[-1])
     print(json.dumps({k: v for k, v in summary.items() if k not in ("first", "last")}))
