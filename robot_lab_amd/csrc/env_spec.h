@@ -113,6 +113,10 @@ inline bool spec_matches(const TablesT<TopoMax>& T) {
       T.n_bodies != SP::N_BODIES)
     return false;
   if (T.n_rewards != SP::N_REW || T.cur_lin || T.cur_ang) return false;
+  // the scanner's grid and mounting: the observation stage of a Spec computes its rays from these constants (env_terms.h spec_scan_slot_xy)
+  if (T.scan_nx != SP::SCAN_NX || T.scan_ny != SP::SCAN_NY || !same(T.scan_res, SP::SCAN_RES) || !same(T.scan_offset, SP::SCAN_OFFSET) ||
+      !same(T.scan_pos[0], SP::SCAN_POS[0]) || !same(T.scan_pos[1], SP::SCAN_POS[1]) || !same(T.scan_pos[2], SP::SCAN_POS[2]))
+    return false;
   if (T.slot_valid != SP::SLOT_VALID) return false;  // the kernel skips the slots this word leaves empty: a sphere the Spec does not know must not exist
   for (int j = 0; j < SP::TP::CL; ++j)  // a joint the Spec composes in sparse form must be axis-aligned in every limb of THIS env's tables
     for (int k = 0; k < NLANE; ++k)

@@ -333,6 +333,41 @@ RL_FN float term_value(const TabT& T, const Uni& u, const float* __restrict__ te
   return f;
 }
 
+// The height scanner's grid on a Spec (env_spec.h SCAN_NX / SCAN_NY): which grid point (ix, iy) - ray iy * NX + ix, x fastest - the I-th load
+// of lane li (of LPE per env) stands for, i.e. ray min(li + LPE * I, N - 1), from compares of li against constants: a slot's row is the row
+// of the trip's first slot plus the wraps of li past the row's end (one when LPE <= NX).  The interpreter's form - a float multiply by 1 / NX
+// and an int / float round trip per ray - gives the same integers (tests/test_spec_tail_emu.py walks every (li, I)).
+template <class SP>
+constexpr int spec_scan_rays() {  // rays of the task's height-scan term; 0: no group carries one
+  if constexpr (SP::ON) {
+    for (int g = 0; g < 2; ++g)
+      for (int i = 0; i < SP::N_OBS[g]; ++i)
+        if (SP::OBS[g][i].kind == OBS_HEIGHT_SCAN) return SP::SCAN_NX * SP::SCAN_NY;
+  }
+  return 0;
+}
+template <class SP, int LPE, int I>
+RL_FN void spec_scan_slot_xy(int li, int& ix, int& iy) {
+  constexpr int NX = SP::SCAN_NX, NY = SP::SCAN_NY, N = NX * NY, base = LPE * I;
+  if constexpr (base >= N) {  // every lane's slot lies behind the last ray
+    ix = NX - 1; iy = NY - 1;
+  } else {
+    constexpr int iy0 = base / NX, rem0 = base % NX, WRAPS = (LPE - 1 + rem0) / NX;
+    const int t = li + rem0;
+    ix = t; iy = iy0;
+    static_for<1, WRAPS + 1>([&](auto wc) __attribute__((always_inline)) {
+      constexpr int w = decltype(wc)::value;
+      const bool past = t >= w * NX;
+      ix = past ? t - w * NX : ix;
+      iy = past ? iy0 + w : iy;
+    });
+    if constexpr (base + LPE > N) {
+      const bool behind = li >= N - base;
+      ix = behind ? NX - 1 : ix;
+      iy = behind ? NY - 1 : iy;
+    }
+  }
+}
 
 template <class Ctx, class TP, class SP = NoSpec>
 struct EnvProgram : EnvLane<Ctx, TP, SP> {
@@ -1187,7 +1222,46 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
       sp.tp[i] = terrain_fetch(this->u, S.terrain, tb, scan_p.x + cy * lx - sy * ly, scan_p.y + sy * lx + cy * ly);
     }
   }
+  // A Spec of the quadruped instances with several sub-lanes per limb whose scan is one trip: the grid, and with it each slot's local offset up
+  // to the lane index, is a constant expression (spec_scan_slot_xy above) - no grid word read from the table image, no ray index turned into
+  // (ix, iy) in floating point.  lx, ly are the same fp32 values: (float)ix - cx0 is exact either way.  (A1 Rough 4096: 30.92 -> 30.55 us,
+  // Go2W 38.42 -> 37.92, profiles/spec_tail_ab.txt.)  -DRL_SPEC_SCAN_TABLES: every Spec reads the grid from the table image, as the
+  // interpreter does (A/B builds, and the emulator build tests/test_spec_tail_emu.py holds the constants against).
+#ifdef RL_SPEC_SCAN_TABLES
+  static constexpr bool SPEC_SCAN = false;
+#else
+  static constexpr bool SPEC_SCAN = SUB > 1 && NW == 0 && spec_scan_rays<SP>() > 0 && spec_scan_rays<SP>() <= SCAN_RB * LPE;
+#endif
+  RL_FN void scan_fetch_trip_spec(float cy, float sy, V3 scan_p, ScanPatches& sp) const {
+    const TerrainBase tb = terrain_base(this->u, pos.x, pos.y);
+    const Uni& un = this->u;
+    const float* hf = S.terrain;
+    const int my_li = li;
+    static_for<0, SCAN_RB>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      constexpr float res = SP::SCAN_RES, cx0 = 0.5f * (float)(SP::SCAN_NX - 1), cy0 = 0.5f * (float)(SP::SCAN_NY - 1);
+      int ix, iy;
+      spec_scan_slot_xy<SP, LPE, i>(my_li, ix, iy);
+      const float lx = ((float)ix - cx0) * res, ly = ((float)iy - cy0) * res;
+      // The rotation into the world frame, contracted the way the compiler contracts the table image's form (scan_fetch_trip: scan_p.x and
+      // scan_p.y are zero on these instances) - cy * lx fused onto the rounded sy * ly, cy * ly onto the rounded sy * lx - and said explicitly:
+      // a slot whose ly is a constant (the grid's first row) otherwise gets the other product fused, one ulp off in a ray's position.
+#if defined(__HIP_DEVICE_COMPILE__)
+      const float dx = scan_p.x + fmaf(cy, lx, -(sy * ly)), dy = scan_p.y + fmaf(cy, ly, sy * lx);
+#else
+      const float dx = scan_p.x + cy * lx - sy * ly, dy = scan_p.y + sy * lx + cy * ly;
+#endif
+      sp.tp[i] = terrain_fetch(un, hf, tb, dx, dy);
+    });
+  }
   RL_FN void scan_fetch(float cy, float sy, V3 scan_p, ScanPatches& sp) const {
+#ifndef RL_ABL_NO_SCAN
+    if constexpr (SPEC_SCAN) {
+      sp.single_trip = true;
+      scan_fetch_trip_spec(cy, sy, scan_p, sp);
+      return;
+    }
+#endif
     const int scan_n = ctx.uniform_i(T.scan_nx * T.scan_ny);
     const bool wanted = ctx.uniform_i(T.obs[0].scan_n + T.obs[1].scan_n) > 0;
     sp.single_trip = wanted && scan_n <= SCAN_RB * LPE;
@@ -1233,7 +1307,9 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
   // the scan's columns of a row: z_sensor - hit_z - offset per ray; the heightfield patches were fetched by scan_fetch()
   RL_FN void write_scan(float* stage, int scan_off, int scan_n, bool corrupt, float s_scale, float s_lo, float s_hi, float cy, float sy, V3 scan_p,
                         const ScanPatches& sp) {
-    const float soff = T.scan_offset;
+    float soff;
+    if constexpr (SPEC_SCAN) soff = SP::SCAN_OFFSET;
+    else soff = T.scan_offset;
     if (sp.single_trip) {
 #pragma unroll
       for (int i = 0; i < SCAN_RB; ++i) {
@@ -1326,7 +1402,10 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
           }
         } else if constexpr (O.kind == OBS_HEIGHT_SCAN) {
 #ifndef RL_ABL_NO_SCAN
-          this->write_scan(stage, O.offset, cx.uniform_i(this->T.scan_nx * this->T.scan_ny), corrupt, O.scale, O.clip_lo, O.clip_hi, A.cy, A.sy, A.scan_p, A.sp);
+          int scan_n;
+          if constexpr (SPEC_SCAN) scan_n = spec_scan_rays<SP>();
+          else scan_n = cx.uniform_i(this->T.scan_nx * this->T.scan_ny);
+          this->write_scan(stage, O.offset, scan_n, corrupt, O.scale, O.clip_lo, O.clip_hi, A.cy, A.sy, A.scan_p, A.sp);
 #endif
         } else {
           if (my_sub == 0) {

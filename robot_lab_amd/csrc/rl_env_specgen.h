@@ -95,6 +95,10 @@ inline std::string spec_source(const rl_env_desc& d, const char* struct_name, co
     }
     out += g == 0 ? "},\n" : "}};\n";
   }
+  // the height scanner's grid (env_terms.h scan_slot_xy: a lane's slot -> ray map from integer arithmetic on these) and mounting
+  add("  static constexpr int SCAN_NX = %d, SCAN_NY = %d;\n", T.scan_nx, T.scan_ny);
+  out += "  static constexpr float SCAN_RES = " + spec_flt(T.scan_res) + ", SCAN_OFFSET = " + spec_flt(T.scan_offset) + ";\n";
+  out += "  static constexpr float SCAN_POS[3] = {" + spec_flt(T.scan_pos[0]) + ", " + spec_flt(T.scan_pos[1]) + ", " + spec_flt(T.scan_pos[2]) + "};\n";
   out += "};\n";
   return done("");
 }
