@@ -685,14 +685,14 @@ void optimiser_step(rl_ppo* p, hipStream_t s) {
 
 // fills (a zeroed) `g` with the problem of `mode` for layer l of network k over `rows` rows (see GemmProb): the operands of either network, the
 // gather through the n0 indices at `idx` and the symmetry tables where the layer's input is the stored batch, the tile grid
-void gemm_prob(GemmProb& g, const rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int mode, int k, int l, int rows) {
-  const Net& N = p->net[k];
+// (net_prob: the same for ONE network of `L` layers whose first layer reads `x0` - what the distillation learner, csrc/learner/rl_distill.inl, shares)
+void net_prob(GemmProb& g, const Net& N, const float* params, int L, const float* x0, int mode, int l, int rows) {
   const int K = N.dims[l], Nn = N.dims[l + 1];
-  const float* x = l > 0 ? N.h[l] : k == 0 ? b->observations : b->privileged_observations;  // the layer's input [rows][K]
-  const float* W = p->params + N.w_off[l];     // [Nn][K]
+  const float* x = l > 0 ? N.h[l] : x0;  // the layer's input [rows][K]
+  const float* W = params + N.w_off[l];  // [Nn][K]
   if (mode == G_FWD) {
-    g.A = x; g.lda = K; g.B = W; g.ldb = K; g.aux = p->params + N.b_off[l]; g.C = N.h[l + 1]; g.ldc = Nn;
-    g.I = rows; g.J = Nn; g.R = K; g.act = l + 1 < p->L;
+    g.A = x; g.lda = K; g.B = W; g.ldb = K; g.aux = params + N.b_off[l]; g.C = N.h[l + 1]; g.ldc = Nn;
+    g.I = rows; g.J = Nn; g.R = K; g.act = l + 1 < L;
   } else if (mode == G_DX) {
     g.A = N.dz[l + 1]; g.lda = Nn; g.B = W; g.ldb = K; g.aux = N.h[l]; g.ldaux = K; g.C = N.dz[l]; g.ldc = K;
     g.I = rows; g.J = K; g.R = Nn;
@@ -701,11 +701,14 @@ void gemm_prob(GemmProb& g, const rl_ppo* p, const rl_ppo_batch* b, const int64_
     g.I = Nn; g.J = K; g.R = rows;
     g.S = N.S[l]; g.chunk = chunk_rows(rows, g.S); g.cstride = (long)Nn * K + Nn;
   }
+  g.tilesJ = tiles_of(g.J); g.ntiles = tiles_of(g.I) * g.tilesJ;
+}
+void gemm_prob(GemmProb& g, const rl_ppo* p, const rl_ppo_batch* b, const int64_t* idx, int n0, int mode, int k, int l, int rows) {
+  net_prob(g, p->net[k], p->params, p->L, k == 0 ? b->observations : b->privileged_observations, mode, l, rows);
   if (mode != G_DX && l == 0) {
     g.gidx = idx;
     if (p->n_sym > 0) { g.sym = p->sym[k]; g.n0 = n0; }
   }
-  g.tilesJ = tiles_of(g.J); g.ntiles = tiles_of(g.I) * g.tilesJ;
 }
 
 // the launches of one mini-batch (see the head of this file); `apply`: APPLY_NONE (the gradient alone), APPLY_FUSED (statistics, learning rate
@@ -1145,3 +1148,6 @@ int rl_ppo_stats_ex(rl_ppo* p, double* out, int32_t n_out, void* stream) {
 }
 
 }  // extern "C"
+
+// the distillation learner (include/rl_distill.h): the same translation unit, so that it launches THESE kernels - nothing is instantiated twice
+#include "learner/rl_distill.inl"

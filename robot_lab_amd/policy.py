@@ -135,18 +135,25 @@ class MlpPolicy:
             self._out = torch.empty(n, self.out_dim, device=self.device, dtype=torch.float32)
         return obs, n
 
-    def forward_pair(self, obs, other: "MlpPolicy", other_obs):
+    def forward_pair(self, obs, other: "MlpPolicy", other_obs, other_out=None):
         """(self(obs), other(other_obs)) from ONE kernel launch - the actor and the critic of a rollout step
-        (rsl_rl PPO.act: `policy.act(obs)` then `policy.evaluate(privileged_obs)`); both batches have the same row count."""
+        (rsl_rl PPO.act: `policy.act(obs)` then `policy.evaluate(privileged_obs)`); both batches have the same row count.
+        `other_out`: a contiguous fp32 [N, other.out_dim] tensor the second network writes instead of its own output buffer (the teacher's
+        actions straight into their slot of a distillation batch)."""
         obs, n = self._prepare(obs)
         other_obs, n2 = other._prepare(other_obs)
         if n != n2 or other.device != self.device:
             raise ValueError("forward_pair needs two batches of the same row count on the same device")
+        if other_out is None:
+            other_out = other._out
+        elif (tuple(other_out.shape) != (n, other.out_dim) or other_out.dtype != self._torch.float32 or other_out.device != self.device
+              or not other_out.is_contiguous()):
+            raise ValueError(f"forward_pair: other_out must be a contiguous float32 tensor ({n}, {other.out_dim}) on {self.device}")
         stream = self._torch.cuda.current_stream(self.device).cuda_stream
         if self.lib.rl_mlp_forward_pair(self.handle, C.c_void_p(obs.data_ptr()), C.c_void_p(self._out.data_ptr()), other.handle,
-                                        C.c_void_p(other_obs.data_ptr()), C.c_void_p(other._out.data_ptr()), n, C.c_void_p(stream)) != 0:
+                                        C.c_void_p(other_obs.data_ptr()), C.c_void_p(other_out.data_ptr()), n, C.c_void_p(stream)) != 0:
             raise RlPolicyError((self.lib.rl_mlp_last_error() or b"").decode())
-        return self._out, other._out
+        return self._out, other_out
 
     def forward_pair_act(self, obs_ptr, other: "MlpPolicy", other_obs_ptr, ep) -> int:
         """The actor (self) / critic (other) launch with the rollout step's stochastic head in its epilogue (include/rl_policy.h

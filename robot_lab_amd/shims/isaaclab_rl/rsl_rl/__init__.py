@@ -68,6 +68,49 @@ class RslRlOnPolicyRunnerCfg(RslRlBaseRunnerCfg):
     algorithm = MISSING
 
 
+# ---- distillation (`.../anymal_d/agents/rsl_rl_distillation_cfg.py`): real containers, so that `class_name` is right after `to_dict()`
+@configclass
+class RslRlMLPModelCfg:
+    @configclass
+    class GaussianDistributionCfg:
+        class_name: str = "GaussianDistribution"
+        init_std: float = 1.0
+        std_type: str = "scalar"
+
+    class_name: str = "MLPModel"
+    hidden_dims: list = MISSING
+    activation: str = MISSING
+    obs_normalization: bool = False
+    distribution_cfg = None
+
+
+@configclass
+class RslRlRNNModelCfg(RslRlMLPModelCfg):
+    class_name: str = "RNNModel"
+    rnn_type: str = MISSING
+    rnn_hidden_dim: int = MISSING
+    rnn_num_layers: int = MISSING
+
+
+@configclass
+class RslRlDistillationAlgorithmCfg:
+    class_name: str = "Distillation"
+    num_learning_epochs: int = MISSING
+    learning_rate: float = MISSING
+    gradient_length: int = MISSING
+    max_grad_norm = None
+    optimizer: str = "adam"
+    loss_type: str = "mse"
+
+
+@configclass
+class RslRlDistillationRunnerCfg(RslRlBaseRunnerCfg):
+    class_name: str = "DistillationRunner"
+    student = MISSING
+    teacher = MISSING
+    algorithm = MISSING
+
+
 def handle_deprecated_rsl_rl_cfg(agent_cfg, installed_version=None):
     return agent_cfg
 

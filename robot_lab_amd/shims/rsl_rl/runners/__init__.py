@@ -164,6 +164,145 @@ class OnPolicyRunner:
         return policy
 
 
+def _given(d, key, default=None):
+    """d[key], with a cfg field that was never filled in (`dataclasses.MISSING`, None) read as `default`"""
+    from dataclasses import MISSING
+
+    v = d.get(key, default)
+    return default if v is None or v is MISSING else v
+
+
+def read_distillation_cfg(train_cfg: dict, env_groups=("policy", "critic")) -> dict:
+    """The keywords of `robot_lab_amd.distill.DistillTrainer` from a `RslRlDistillationRunnerCfg.to_dict()` in the reference file's spelling
+    (`.../anymal_d/agents/rsl_rl_distillation_cfg.py`).  What this stand-in does not implement is refused with a reason, never ignored."""
+    if "policy" in train_cfg and _given(train_cfg, "policy") is not None:
+        raise NotImplementedError("stand-in DistillationRunner: `policy=dict(class_name=\"StudentTeacher\", ...)` is rsl_rl 3.0.1's spelling and is not read "
+                                  "here: give the two networks as `student` / `teacher` model cfgs (RslRlMLPModelCfg), as the reference's "
+                                  "rsl_rl_distillation_cfg.py does")
+    models = {}
+    for role in ("student", "teacher"):
+        m = _given(train_cfg, role)
+        if not isinstance(m, dict):
+            raise ValueError(f"stand-in DistillationRunner: the cfg has no `{role}` model cfg (RslRlMLPModelCfg: hidden_dims, activation, obs_normalization, distribution_cfg)")
+        if _given(m, "rnn_type") is not None or m.get("class_name") == "RNNModel":
+            raise NotImplementedError(f"stand-in DistillationRunner: the {role} is a recurrent model (rnn_type={m.get('rnn_type')!r}); recurrent students and "
+                                      "teachers are not implemented - use the feed-forward RslRlMLPModelCfg")
+        if _given(m, "activation", "elu") != "elu":
+            raise NotImplementedError(f"stand-in DistillationRunner: {role} activation={m.get('activation')!r}; ELU networks only (the fused inference kernels "
+                                      "and the HIP learner implement ELU)")
+        if _given(m, "hidden_dims") is None:
+            raise ValueError(f"stand-in DistillationRunner: the {role} model cfg has no hidden_dims")
+        models[role] = m
+    if _given(models["student"], "obs_normalization", False):
+        raise NotImplementedError("stand-in DistillationRunner: student obs_normalization=True is not implemented (the student's statistics would have to be "
+                                  "updated inside the captured collection loop and applied in the learner); set it to False")
+    alg = _given(train_cfg, "algorithm", {})
+    if alg.get("class_name", "Distillation") != "Distillation":
+        raise NotImplementedError(f"stand-in DistillationRunner: algorithm.class_name={alg.get('class_name')!r}, only \"Distillation\"")
+    if _given(alg, "optimizer", "adam") != "adam":
+        raise NotImplementedError(f"stand-in DistillationRunner: optimizer={alg.get('optimizer')!r}; only \"adam\" (torch.optim.Adam's defaults, which the HIP "
+                                  "learner's step kernel implements)")
+    groups = dict(_given(train_cfg, "obs_groups", {}) or {})
+    chosen = {}
+    for role in ("student", "teacher"):
+        sets = list(groups.get(role, ["policy"]))
+        if len(sets) != 1:
+            raise NotImplementedError(f"stand-in DistillationRunner: obs_groups[{role!r}] = {sets}: exactly one observation group per network is wired to the "
+                                      "fused inference kernels (no concatenation of groups)")
+        if sets[0] not in env_groups:
+            raise ValueError(f"stand-in DistillationRunner: obs_groups[{role!r}] = {sets}: the env has no observation group {sets[0]!r} (it has {sorted(env_groups)})")
+        chosen[role] = sets[0]
+    dist = _given(models["student"], "distribution_cfg", {}) or {}
+    kw = dict(num_steps_per_env=int(_given(train_cfg, "num_steps_per_env", 24)), student_hidden=tuple(models["student"]["hidden_dims"]),
+              teacher_hidden=tuple(models["teacher"]["hidden_dims"]), init_noise_std=float(_given(dist, "init_std", 0.1)),
+              student_group=chosen["student"], teacher_group=chosen["teacher"],
+              teacher_obs_normalization=bool(_given(models["teacher"], "obs_normalization", False)), seed=int(_given(train_cfg, "seed", 42)),
+              num_learning_epochs=int(_given(alg, "num_learning_epochs", 1)), gradient_length=int(_given(alg, "gradient_length", 15)),
+              learning_rate=float(_given(alg, "learning_rate", 1e-3)), max_grad_norm=_given(alg, "max_grad_norm"), loss_type=_given(alg, "loss_type", "mse"))
+    return kw
+
+
 class DistillationRunner:
-    def __init__(self, *a, **k):
-        raise NotImplementedError("stand-in for rsl_rl: DistillationRunner is not provided (no robot_lab velocity task uses it)")
+    """rsl_rl's `DistillationRunner` as the reference's scripts use it (train.py:205-217): the same calls as `OnPolicyRunner`.  Collection is
+    robot_lab_amd/distill_collect.py (student and teacher in one launch, one hipGraph launch per iteration), the update robot_lab_amd/distill.py
+    or - `RL_LEARNER=hip` - robot_lab_amd/distill_hip.py.  `load(path)` goes through `StudentTeacher.load_state_dict`: a PPO checkpoint becomes the
+    teacher (iteration 0, fresh optimiser), a distillation checkpoint resumes iteration and optimiser.  Checkpoints are `model_<it>.pt` in rsl_rl's layout."""
+
+    def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device: str = "cpu"):
+        from robot_lab_amd.dist import LearnerGroup, rank_info
+        from robot_lab_amd.distill import DistillTrainer
+
+        world = rank_info()[2]
+        if world > 1:  # before a process group is formed: the other ranks would wait for a collective that never comes
+            raise NotImplementedError(f"stand-in DistillationRunner: a LearnerGroup of {world} ranks is not implemented (the distillation "
+                                      "learners do not exchange gradients): run one rank")
+        self.env, self.cfg, self.log_dir, self.device = env, train_cfg, log_dir, device
+        self.learner = learner_from_env()
+        inner = env.unwrapped
+        kw = read_distillation_cfg(train_cfg, tuple(inner.get_observations().keys()))
+        self.group = LearnerGroup(device)  # (a world of one: disabled, no process group)
+        self.trainer = DistillTrainer(inner, learner=self.learner, clip_actions=_given(train_cfg, "clip_actions", getattr(env, "clip_actions", None)), **kw)
+        self.alg = self.trainer.alg
+        self.save_interval = int(_given(train_cfg, "save_interval", 50))
+        self.current_learning_iteration = 0
+        self.git_status_repos = []
+        self.history = []  # the statistics of every iteration of learn()
+
+    def add_git_repo_to_log(self, path):
+        self.git_status_repos.append(path)
+
+    def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False):
+        if not self.alg.policy.loaded_teacher:
+            raise ValueError("DistillationRunner.learn: no teacher is loaded - call load(<PPO checkpoint of the teacher>) first (train.py does, for "
+                             "every Distillation cfg)")
+        env = self.env.unwrapped
+        if init_at_random_ep_len:
+            env.episode_length_buf = torch.randint(0, int(env.max_episode_length), (env.num_envs,))
+        if self.log_dir:
+            os.makedirs(self.log_dir, exist_ok=True)
+        start = self.current_learning_iteration
+        t0 = time.time()
+        for it in range(start, start + num_learning_iterations):
+            out = self.trainer.iterate()
+            self.history.append(out)
+            self.current_learning_iteration = it + 1
+            steps = self.trainer.storage.num_transitions_per_env * env.num_envs
+            print(f"[rsl_rl stand-in] distillation {it + 1}/{start + num_learning_iterations}  behavior loss {out['behavior']:.6f}  mean reward/step "
+                  f"{out['mean_reward']:+.4f}  grad norm {out['grad_norm']:.3e}  lr {out['learning_rate']:.1e}  "
+                  f"{steps * (it + 1 - start) / max(time.time() - t0, 1e-9):.0f} steps/s", flush=True)
+            if self.log_dir and (it + 1) % self.save_interval == 0:
+                self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
+        if self.log_dir:
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+        if self.learner == "hip":
+            self.alg.store_into(self.alg.policy)  # `runner.alg.policy` is current after learn() (exporters, play.py)
+
+    def save(self, path: str, infos=None):
+        if self.learner == "hip":
+            self.alg.store_into(self.alg.policy)
+            optimizer_state = self.alg.optimizer_state_dict()
+        else:
+            optimizer_state = self.alg.optimizer.state_dict()
+        torch.save({"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": optimizer_state,
+                    "iter": self.current_learning_iteration, "infos": infos}, path)
+
+    def load(self, path: str, load_optimizer: bool = True, map_location=None):
+        d = torch.load(path, map_location=map_location or self.trainer.device, weights_only=False)
+        resumed = self.trainer.load_state_dict(d["model_state_dict"])
+        if resumed:  # a distillation checkpoint: iteration and optimiser continue; a teacher's PPO checkpoint starts at 0 with a fresh optimiser
+            if load_optimizer and d.get("optimizer_state_dict"):
+                if self.learner == "hip":
+                    self.alg.load_optimizer_state_dict(d["optimizer_state_dict"])
+                else:
+                    self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
+            self.current_learning_iteration = int(d.get("iter", 0))
+        return d.get("infos")
+
+    def get_inference_policy(self, device=None):
+        student = self.trainer.student  # the fused HIP inference kernel, fed by the push after every update
+
+        def policy(obs):
+            obs = obs if torch.is_tensor(obs) else obs[self.trainer.student_group]
+            return student(obs)
+
+        return policy

@@ -45,6 +45,8 @@ def main():
                     help="with --obs-normalization: the learners normalise the raw stored rows themselves (needed together with --symmetry / --mirror-loss)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
+    ap.add_argument("--save", default=None, metavar="PATH", help="also write a checkpoint in the runner's layout (model_state_dict / optimizer_state_dict / iter / infos): "
+                    "what tools/distill_demo.py --teacher and the runners' load() read")
     ap.add_argument("--also-terminate-on", default="", help="DIAGNOSTIC, not the reference's cfg: regex of body names added to the illegal-contact termination")
     a = ap.parse_args()
     if not a.symmetry and (a.mirror_loss is not None or a.no_data_augmentation):
@@ -118,6 +120,11 @@ def main():
     with open(os.path.join(a.out, f"train_demo_{tag}.json"), "w") as f:
         json.dump(dict(summary=summary, log=log), f, indent=1)
     torch.save(tr.state_dict(), os.path.join(a.out, f"train_demo_{tag}.pt"))
+    if a.save:
+        optimizer_state = tr.alg.optimizer_state_dict() if a.learner == "hip" else tr.alg.optimizer.state_dict()
+        os.makedirs(os.path.dirname(os.path.abspath(a.save)), exist_ok=True)
+        torch.save({"model_state_dict": tr.state_dict(), "optimizer_state_dict": optimizer_state, "iter": a.iterations, "infos": None}, a.save)
+        print(f"checkpoint in the runner's layout: {a.save}")
     env.close()
 
 
