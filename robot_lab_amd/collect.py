@@ -35,9 +35,30 @@ class Collector:
 
     def __init__(self, env, actor, critic, storage, action_std: torch.Tensor, gamma: float = 0.99, lam: float = 0.95,
                  normalize_advantage: bool = True, use_graph: bool = True, clip_actions: float | None = None, overlap: bool = False, critic_small: bool = True,
-                 fused_act: bool = True, normalizers=None):
+                 fused_act: bool | None = None, normalizers=None, recurrent=None):
         self.env, self.actor, self.critic, self.storage = env, actor, critic, storage
         self.overlap = overlap
+        # a robot_lab_amd.lstm.RecurrentState: the memories in front of `actor` / `critic` (MLP heads of input width H) - see `_iteration_recurrent`
+        self.recurrent = recurrent
+        if recurrent is not None:
+            if overlap:
+                raise NotImplementedError("Collector: overlap=True with recurrent= is not implemented: the critic's side stream would need the critic cell's "
+                                          "step, state record and reset ordered against the main stream's pair launch; use the serial loop (overlap=False)")
+            if fused_act:
+                raise NotImplementedError("Collector: fused_act=True with recurrent= is not implemented: the fused act epilogue stores the MLP launch's INPUT rows "
+                                          "into the slot, which are the memories' outputs h', not the observations; leave fused_act unset (the unfused act runs)")
+            if normalizers is not None and any(n is not None for n in normalizers):
+                raise NotImplementedError("Collector: normalizers together with recurrent= are not implemented (recurrence with observation normalisation is a "
+                                          "follow-up); drop one of them")
+            if recurrent.num_envs != storage.num_envs or recurrent.T != storage.num_transitions_per_env:
+                raise ValueError(f"Collector: the RecurrentState is sized {recurrent.T} x {recurrent.num_envs}, the storage "
+                                 f"{storage.num_transitions_per_env} x {storage.num_envs}")
+            if actor.in_dim != recurrent.cell_a.hidden or critic.in_dim != recurrent.cell_c.hidden:
+                raise ValueError(f"Collector: the MLP heads read {actor.in_dim} / {critic.in_dim} columns, the memories give "
+                                 f"{recurrent.cell_a.hidden} / {recurrent.cell_c.hidden}")
+            fused_act = False
+        elif fused_act is None:
+            fused_act = True
         # (actor_norm | None, critic_norm | None): robot_lab_amd.obsnorm.ObsNormalizer handles of the two observation groups - see `_iteration_normalized`
         self.normalizers = tuple(normalizers) if normalizers is not None and any(n is not None for n in normalizers) else None
         if self.normalizers is not None:
@@ -67,6 +88,8 @@ class Collector:
             return self._iteration_overlapped(obs)
         if self.normalizers is not None:
             return self._iteration_normalized(obs)
+        if self.recurrent is not None:
+            return self._iteration_recurrent(obs)
         st, env = self.storage, self.env
         st.clear()
         for _ in range(self.T):
@@ -112,6 +135,28 @@ class Collector:
                 (an or cn).update(obs["policy" if an is not None else "critic"])
         last = obs["critic"] if cn is None else cn.apply(obs["critic"], out=self._norm_obs[1])
         st.compute_returns(self.critic(last), self.gamma, self.lam, self.normalize)
+        return obs
+
+    def _iteration_recurrent(self, obs):
+        """THE RULE's collection (robot_lab_amd/recurrent.py) per step: ONE pair launch of the two LSTM cells (csrc/rl_lstm.hip) - the resets of the
+        previous step's dones applied, the state each cell starts from saved into slot t -, the MLP heads on (h_a', h_c'), the UNFUSED act on the
+        raw observations, env.step.  The dones of step t are the reset mask of step t + 1 WITHOUT a launch of their own: the env kernel writes
+        them into the storage's slot t (0 / 1 bytes), and the cell launch of step t + 1 reads that slot as its reset vector.  Step 0 reads the
+        state's own reset vector, which takes the last slot once per iteration (the storage's slots are rewritten by then).  The bootstrap
+        call writes into scratch and commits nothing."""
+        st, env, rec = self.storage, self.env, self.recurrent
+        ckey = getattr(rec, "critic_group", "critic")
+        st.clear()
+        dones = st.dones.view(torch.uint8)
+        for t in range(self.T):
+            ha, hc = rec.step(t, obs["policy"], obs[ckey], rec.reset if t == 0 else dones[t - 1])
+            mean, values = self.actor.forward_pair(ha, self.critic, hc)
+            actions = st.act(obs["policy"], obs[ckey], mean, self.std, values)
+            if self.clip_actions is not None:
+                actions = actions.clamp(-self.clip_actions, self.clip_actions)
+            obs, _, _, _, _ = env.step(actions, rollout=st, gamma=self.gamma)
+        rec.reset.copy_(dones[self.T - 1])
+        st.compute_returns(self.critic(rec.bootstrap(obs[ckey], rec.reset)), self.gamma, self.lam, self.normalize)
         return obs
 
     def _iteration_overlapped(self, obs):

@@ -168,6 +168,56 @@ class PPO:
         perm, sign = self._sym_tensors[key]
         return torch.cat([sign[s] * x[:, perm[s]] for s in range(perm.shape[0])], 0)
 
+    def minibatch_loss(self, stats, mb_actions, mean, std, value, n, logp_old, adv, values, returns, mu_old, sigma_old, mirror=None):
+        """The loss of one mini-batch from the networks' outputs on its rows (`mean`, `std`, `value`) and the stored quantities of the same rows
+        (`mu_old` / `sigma_old`: of the first `n`, the stored copy): log-probability, entropy, the KL statistic and the adaptive learning rate it
+        drives, the clipped surrogate, the (clipped) value loss.  The statistics are accumulated into `stats`.  One copy: the feed-forward update
+        below and the recurrent one (robot_lab_amd/recurrent.py) differ only in how `mean` and `value` were computed."""
+        logp = gaussian_log_prob(mb_actions, mean, std)
+        entropy = gaussian_entropy(std)
+        if self.schedule == "adaptive" and self.desired_kl is not None:
+            with torch.inference_mode():
+                kl = gaussian_kl(mu_old, sigma_old, mean[:n], std[:n]).mean()
+                if self.group is not None:
+                    kl = self.group.mean(kl)  # the same statistic on every rank -> the same learning rate on every rank
+                if kl > 2.0 * self.desired_kl:
+                    self.learning_rate = max(1e-5, self.learning_rate / 1.5)
+                elif 0.0 < kl < self.desired_kl / 2.0:
+                    self.learning_rate = min(1e-2, self.learning_rate * 1.5)
+                for g in self.optimizer.param_groups:
+                    g["lr"] = self.learning_rate
+                stats["kl"] += float(kl)
+        ratio = torch.exp(logp - logp_old)
+        a = adv
+        surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
+        if self.use_clipped_value_loss:
+            v_clipped = values + (value - values).clamp(-self.clip_param, self.clip_param)
+            value_loss = torch.max((value - returns) ** 2, (v_clipped - returns) ** 2).mean()
+        else:
+            value_loss = ((returns - value) ** 2).mean()
+        loss = surrogate + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+        if mirror is not None:
+            loss = loss + self.mirror_loss * mirror
+            stats["mirror_loss"] += float(mirror.detach())
+        stats["value_loss"] += float(value_loss.detach())
+        stats["surrogate_loss"] += float(surrogate.detach())
+        stats["entropy"] += float(entropy.detach().mean())
+        return loss
+
+    def optimizer_step(self, loss):
+        """backward, the group's all-reduce, the clipped gradient norm, Adam, the floor of std"""
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        if self.group is not None:
+            self.group.reduce_gradients(self.policy)  # SUM / world, one flat all-reduce (rsl_rl `reduce_parameters`)
+        nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+        self.optimizer.step()
+        # a standard deviation pushed to (or through) zero would put NaN into the log-densities: the PARAMETER is floored, so that the
+        # collector's sampling kernel, the stored sigma and this update all see the same distribution (rsl_rl 3.0.1 does not
+        # clamp at all and fails with torch's Normal on a non-positive std; 1e-6 is far below any std training reaches)
+        with torch.no_grad():
+            self.policy.std.clamp_(min=1e-6)
+
     def update(self, storage, generator: torch.Generator | None = None) -> dict:
         """With `symmetry`: every mini-batch of n rows is evaluated on n_sym n rows - observations, critic observations and actions mirrored
         (`_mirrored`), old log-prob, advantage, return and value of a row repeated for each of its copies; both losses are means over the
@@ -217,47 +267,10 @@ class PPO:
                     mirror = ((mean[n:] - self._mirrored("act", mean[:n].detach())[n:]) ** 2).mean()
                     if not self.data_augmentation:
                         mean, std = mean[:n], std[:n]
-                logp = gaussian_log_prob(mb_actions, mean, std)
                 value = critic(mb_cobs).view(-1)
-                entropy = gaussian_entropy(std)
-                if self.schedule == "adaptive" and self.desired_kl is not None:
-                    with torch.inference_mode():
-                        kl = gaussian_kl(mu_old[idx], sigma_old[idx], mean[:n], std[:n]).mean()
-                        if self.group is not None:
-                            kl = self.group.mean(kl)  # the same statistic on every rank -> the same learning rate on every rank
-                        if kl > 2.0 * self.desired_kl:
-                            self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-                        elif 0.0 < kl < self.desired_kl / 2.0:
-                            self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-                        for g in self.optimizer.param_groups:
-                            g["lr"] = self.learning_rate
-                        stats["kl"] += float(kl)
-                ratio = torch.exp(logp - logp_old[rep])
-                a = adv[rep]
-                surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
-                if self.use_clipped_value_loss:
-                    v_clipped = values[rep] + (value - values[rep]).clamp(-self.clip_param, self.clip_param)
-                    value_loss = torch.max((value - returns[rep]) ** 2, (v_clipped - returns[rep]) ** 2).mean()
-                else:
-                    value_loss = ((returns[rep] - value) ** 2).mean()
-                loss = surrogate + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
-                if self.mirror_loss is not None:
-                    loss = loss + self.mirror_loss * mirror
-                    stats["mirror_loss"] += float(mirror.detach())
-                self.optimizer.zero_grad(set_to_none=True)
-                loss.backward()
-                if self.group is not None:
-                    self.group.reduce_gradients(self.policy)  # SUM / world, one flat all-reduce (rsl_rl `reduce_parameters`)
-                nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
-                self.optimizer.step()
-                # a standard deviation pushed to (or through) zero would put NaN into the log-densities: the PARAMETER is floored, so that the
-                # collector's sampling kernel, the stored sigma and this update all see the same distribution (rsl_rl 3.0.1 does not
-                # clamp at all and fails with torch's Normal on a non-positive std; 1e-6 is far below any std training reaches)
-                with torch.no_grad():
-                    self.policy.std.clamp_(min=1e-6)
-                stats["value_loss"] += float(value_loss.detach())
-                stats["surrogate_loss"] += float(surrogate.detach())
-                stats["entropy"] += float(entropy.detach().mean())
+                loss = self.minibatch_loss(stats, mb_actions, mean, std, value, n, logp_old[rep], adv[rep], values[rep], returns[rep], mu_old[idx], sigma_old[idx],
+                                           mirror if self.mirror_loss is not None else None)
+                self.optimizer_step(loss)
                 n_updates += 1
         out = {k: v / max(n_updates, 1) for k, v in stats.items()}
         out["learning_rate"] = self.learning_rate
@@ -295,6 +308,29 @@ class NormalizedBatch:
 MAX_INPUT_WIDTH = 512  # = RL_MLP_MAX_WIDTH (include/rl_policy.h) = RL_PPO_MAX_WIDTH (include/rl_ppo.h): widest layer, the input included
 
 
+def check_recurrent_trainer(rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, learner, symmetry, group, normalization, ppo_kw):
+    """What `Trainer(rnn_type=...)` does not combine with is refused with a reason, never ignored (no device needed)."""
+    from .recurrent import check_rnn_cfg
+
+    check_rnn_cfg("Trainer", rnn_type, rnn_hidden_dim, rnn_num_layers)
+    if critic_group not in ("critic", "policy"):
+        raise ValueError(f"Trainer: critic_group must be \"critic\" or \"policy\", not {critic_group!r}")
+    if learner == "hip":
+        raise NotImplementedError("Trainer: learner=\"hip\" with a recurrent policy is not implemented: back-propagation through time in the HIP learner is the "
+                                  "follow-up; the recurrent update runs on learner=\"torch\" (robot_lab_amd/recurrent.py), the collection on the HIP cell")
+    if learner != "torch":
+        raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
+    if symmetry is not None or ppo_kw.get("mirror_loss") is not None:
+        raise NotImplementedError("Trainer: symmetry= / mirror_loss= with a recurrent policy is not implemented: mirroring a trajectory through the memory (whose "
+                                  "saved state has no mirror table) is not defined here; drop symmetry= or rnn_type=")
+    if normalization:
+        raise NotImplementedError("Trainer: the observation-normalisation flags with a recurrent policy are not implemented: the statistics' update would sit "
+                                  "between the cell launch and its state record inside the captured loop; drop the *_obs_normalization flags or rnn_type=")
+    if group is not None and getattr(group, "world_size", 1) > 1:
+        raise NotImplementedError(f"Trainer: a recurrent policy with a group of {group.world_size} ranks is not implemented: the recurrent update walks "
+                                  "contiguous blocks of envs in order and the ranks' gradient exchange per block is not decided here; run one rank")
+
+
 class Trainer:
     """collect (HIP, one graph launch) -> update -> push parameters, repeated: `OnPolicyRunner.learn` in miniature.
     `learner="torch"` (default): `PPO` above, autograd; `learner="hip"`: `ppo_hip.HipPPO`, the same rule as HIP kernels (with a `group`: its split update
@@ -311,17 +347,28 @@ class Trainer:
     `normalize_in_learner=True` (with a normalisation flag): the update reads the RAW storage and the learner normalises - the torch learner
     through the modules' forward, the HIP learner in its first layer's operand fetch (`HipPPO(obs_normalizers=...)`), both behind the mirror, as
     rsl_rl does: the mirrored raw row is normalised.  No normalised copy of the batch is allocated.  This is what `symmetry` / `mirror_loss`
-    need together with normalised observations; the default stays the scratch matrices of `NormalizedBatch`."""
+    need together with normalised observations; the default stays the scratch matrices of `NormalizedBatch`.
+    `rnn_type="lstm"`, `rnn_hidden_dim`, `rnn_num_layers=1`, `critic_group="critic" | "policy"`: a recurrent policy (rsl_rl `ActorCriticRecurrent`; the rule
+    is robot_lab_amd/recurrent.py) - `actor_hidden` / `critic_hidden` are then the MLP heads behind the two memories.  The cells run as HIP kernels in
+    the captured collection loop, the update is `recurrent.RecurrentPPO` (torch).  Refused with `learner="hip"`, "gru", several layers, `symmetry`,
+    the normalisation flags and a `group` of more than one rank."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
                  critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None,
-                 actor_obs_normalization=False, critic_obs_normalization=False, normalize_in_learner=False, **ppo_kw):
+                 actor_obs_normalization=False, critic_obs_normalization=False, normalize_in_learner=False, rnn_type=None, rnn_hidden_dim=256,
+                 rnn_num_layers=1, critic_group="critic", **ppo_kw):
         from .collect import Collector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
 
+        self.recurrent = None
+        if rnn_type is not None:  # refused before the env is touched: what a recurrent policy does not combine with
+            check_recurrent_trainer(rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, learner, symmetry, group,
+                                    actor_obs_normalization or critic_obs_normalization or normalize_in_learner, ppo_kw)
+        elif critic_group != "critic":
+            raise NotImplementedError("Trainer: critic_group is read by a recurrent policy only (rnn_type=\"lstm\"); the feed-forward critic reads the critic group")
         obs, _ = env.reset()
-        od, cd, A = obs["policy"].shape[1], obs["critic"].shape[1], env.num_actions
+        od, cd, A = obs["policy"].shape[1], obs[critic_group].shape[1], env.num_actions
         for name, width in (("policy", od), ("critic", cd)):  # before anything is built: the kernels would fail deep inside otherwise
             if width > MAX_INPUT_WIDTH:
                 hist = (getattr(env, "obs_history", None) or {}).get(name)
@@ -342,6 +389,10 @@ class Trainer:
                                       "keep their own statistics or reduce them is not decided here (run one rank, or drop the *_obs_normalization flags)")
         torch.manual_seed(seed)
         self.env, self.device = env, obs["policy"].device
+        if rnn_type is not None:
+            self._init_recurrent(env, od, cd, A, num_steps_per_env, gamma, lam, seed, use_graph, actor_hidden, critic_hidden, init_noise_std, clip_actions,
+                                 rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, ppo_kw)
+            return
         if normalized:
             self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std, bool(actor_obs_normalization),
                                       bool(critic_obs_normalization)).to(self.device)
@@ -398,13 +449,46 @@ class Trainer:
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self.iteration = 0
 
+    def _init_recurrent(self, env, od, cd, A, num_steps_per_env, gamma, lam, seed, use_graph, actor_hidden, critic_hidden, init_noise_std, clip_actions,
+                        rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, ppo_kw):
+        """`rnn_type="lstm"`: `recurrent.ActorCriticRecurrent` under `recurrent.RecurrentPPO` (torch), the two cells (csrc/rl_lstm.hip) and the MLP heads of
+        input width H in the recurrent `Collector`; all of them are pushed after every update."""
+        from .collect import Collector
+        from .lstm import LstmCell, RecurrentState
+        from .policy import MlpPolicy
+        from .recurrent import ActorCriticRecurrent, RecurrentBatch, RecurrentPPO
+        from .rollout import RolloutStorage
+
+        self.policy = ActorCriticRecurrent(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std, rnn_type, rnn_hidden_dim, rnn_num_layers).to(self.device)
+        self.normalized, self.normalize_in_learner, self.normalizers, self.symmetry, self.learner = (), False, None, None, "torch"
+        self.alg = RecurrentPPO(self.policy, **ppo_kw)
+        lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
+        host = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        dev = str(self.device)
+        self.actor = MlpPolicy([host(x.weight) for x in lin(self.policy.actor)], [host(x.bias) for x in lin(self.policy.actor)], "elu", device=dev)
+        self.critic = MlpPolicy([host(x.weight) for x in lin(self.policy.critic)], [host(x.bias) for x in lin(self.policy.critic)], "elu", device=dev)
+        self.recurrent = RecurrentState(LstmCell.from_module(self.policy.memory_a.rnn, device=dev), LstmCell.from_module(self.policy.memory_c.rnn, device=dev),
+                                        env.num_envs, num_steps_per_env)
+        self.recurrent.critic_group = critic_group
+        self.storage = RolloutStorage(env.num_envs, num_steps_per_env, od, cd, A, seed=seed, device=dev)
+        self.std = self.policy.std.detach().clone()
+        rec = self.recurrent
+        self._batch = RecurrentBatch(self.storage, (rec.h_a[0], rec.c_a[0]), (rec.h_c[0], rec.c_c[0]))
+        self.collector = Collector(env, self.actor, self.critic, self.storage, self.std, gamma=gamma, lam=lam, use_graph=use_graph, clip_actions=clip_actions,
+                                   recurrent=rec)
+        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        self.iteration = 0
+
     def __repr__(self):
         sym = f", symmetry={self.symmetry!r}{mirror_repr(self.alg)}" if self.symmetry is not None else ""
+        sym += f", recurrent=lstm({self.policy.rnn_hidden_dim})" if self.recurrent is not None else ""
         sym += f", obs_normalization={list(self.normalized)}" if self.normalized else ""
         sym += ", normalize_in_learner=True" if self.normalize_in_learner else ""
         return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration}{sym})"
 
     def _modules(self):
+        if self.recurrent is not None:
+            return ()
         return (self.policy.actor_obs_normalizer, self.policy.critic_obs_normalizer)
 
     def sync_normalizers(self):
@@ -439,6 +523,9 @@ class Trainer:
         self.actor.load_linear_layers(self.policy.actor)
         self.critic.load_linear_layers(self.policy.critic)
         self.std.copy_(self.policy.std.detach().clamp_min(1e-6))
+        if self.recurrent is not None:  # device to device on this stream, which the next collection follows (rl_lstm_set_weights_device)
+            self.recurrent.cell_a.load_module(self.policy.memory_a.rnn)
+            self.recurrent.cell_c.load_module(self.policy.memory_c.rnn)
 
     def update_batch(self):
         """the filled storage as the learner reads it: the storage itself (no normalisation, or `normalize_in_learner`: the learner normalises the

@@ -185,7 +185,8 @@ class RslRlVecEnvWrapper:
 
 class _PolicyExporter:
     """[UPSTREAM isaaclab_rl.rsl_rl.exporter] what `play.py:209-233` exports: normaliser followed by the actor MLP (the
-    feed-forward policies of the reference's agent cfgs; recurrent policies are not used by any robot_lab task)."""
+    feed-forward policies of the reference's agent cfgs).  The reference's `rsl_rl_recurrent_cfg_entry_point` tasks train recurrent policies
+    (robot_lab_amd/recurrent.py); exporting one is refused with a reason: the exported module would have to carry the memory's state."""
 
     @staticmethod
     def build(policy, normalizer=None):
@@ -193,6 +194,10 @@ class _PolicyExporter:
 
         import torch
 
+        if getattr(policy, "is_recurrent", False) or hasattr(policy, "memory_a"):
+            raise NotImplementedError("export_policy_as_*: a recurrent policy (ActorCriticRecurrent) is not exported: the exporter writes normaliser + actor MLP, "
+                                      "and the actor MLP alone reads the memory's output, not observations; an exported module with the LSTM state and a "
+                                      "reset() entry is not implemented - run the policy through runner.get_inference_policy()")
         actor = getattr(policy, "actor", None)
         if actor is None:
             actor = getattr(policy, "student", None)

@@ -9,7 +9,10 @@ one hipGraph launch per iteration (robot_lab_amd/collect.py), the update is robo
 environment, the HIP learner of robot_lab_amd/ppo_hip.py, on one GPU or under `--distributed` -, checkpoints use rsl_rl's layout
 (`model_<it>.pt`: model_state_dict / optimizer_state_dict / iter / infos) with either learner, and one learner's checkpoint resumes the other.
 `policy.actor_obs_normalization` / `policy.critic_obs_normalization` reach the `Trainer` (csrc/rl_obsnorm.hip); the checkpoint then carries
-rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` buffers."""
+rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` buffers.
+A recurrent cfg - `policy.class_name="ActorCriticRecurrent"`, or the reference's `actor=` / `critic=` RNNModel cfgs (robot_lab_amd.recurrent.read_recurrent_cfg) -
+builds `Trainer(rnn_type="lstm", ...)`: the LSTM cells run in the captured collection (csrc/rl_lstm.hip), the update is the torch learner's; checkpoints carry
+rsl_rl's `memory_a.rnn.*` / `memory_c.rnn.*` keys, `get_inference_policy()` is stateful with `reset(dones)`."""
 from __future__ import annotations
 
 import os
@@ -32,7 +35,17 @@ class OnPolicyRunner:
 
         self.env, self.cfg, self.log_dir, self.device = env, train_cfg, log_dir, device
         self.learner = learner_from_env()
-        pol, alg = dict(train_cfg.get("policy", {})), dict(train_cfg.get("algorithm", {}))
+        from robot_lab_amd.recurrent import RecurrentInferencePolicy, read_recurrent_cfg
+
+        pol, alg = dict(train_cfg.get("policy") or {}), dict(train_cfg.get("algorithm", {}))
+        # a recurrent cfg (policy.class_name="ActorCriticRecurrent", or the reference's actor= / critic= RNNModel cfgs): the Trainer keywords, else None
+        recurrent = read_recurrent_cfg(train_cfg)
+        if recurrent is not None:
+            if self.learner == "hip":
+                raise NotImplementedError("stand-in runner: RL_LEARNER=hip with a recurrent cfg is not implemented: back-propagation through time in the HIP "
+                                          "learner is the follow-up; unset RL_LEARNER (the torch learner runs the recurrent update, the HIP cell the collection)")
+            pol = dict(class_name="ActorCritic", actor_hidden_dims=recurrent.pop("actor_hidden"), critic_hidden_dims=recurrent.pop("critic_hidden"),
+                       init_noise_std=recurrent.pop("init_noise_std"), noise_std_type=pol.get("noise_std_type", "scalar"))
         if pol.get("class_name", "ActorCritic") != "ActorCritic" or alg.get("class_name", "PPO") != "PPO":
             raise NotImplementedError(f"stand-in runner: ActorCritic + PPO only, got {pol.get('class_name')} / {alg.get('class_name')}")
         if pol.get("activation", "elu") != "elu":
@@ -51,7 +64,7 @@ class OnPolicyRunner:
         # options this stand-in does not implement are refused, never ignored (a silently different learner is worse than none)
         groups = dict(train_cfg.get("obs_groups") or {})
         actor_set = groups.get("policy", groups.get("actor", ["policy"]))
-        if list(actor_set) != ["policy"] or list(groups.get("critic", ["critic"])) != ["critic"]:
+        if recurrent is None and (list(actor_set) != ["policy"] or list(groups.get("critic", ["critic"])) != ["critic"]):
             raise NotImplementedError(f"stand-in runner: obs_groups {groups} - only policy <- ['policy'], critic <- ['critic'] (what every "
                                       f"robot_lab velocity cfg but ANYmal-D's uses) is wired to the fused inference kernels")
         if pol.get("noise_std_type", "scalar") != "scalar":
@@ -72,9 +85,14 @@ class OnPolicyRunner:
                                lam=float(alg.get("lam", 0.95)), seed=int(train_cfg.get("seed", 42)), actor_hidden=pol.get("actor_hidden_dims", (512, 256, 128)),
                                critic_hidden=pol.get("critic_hidden_dims", (512, 256, 128)), init_noise_std=float(pol.get("init_noise_std", 1.0)),
                                clip_actions=getattr(env, "clip_actions", None), group=self.group if self.group.enabled else None, learner=self.learner,
-                               **{k: v for k, v in norm.items() if v}, **{k: alg[k] for k in keys if k in alg})
+                               **{k: v for k, v in norm.items() if v}, **(recurrent or {}), **{k: alg[k] for k in keys if k in alg})
         self.alg = self.trainer.alg
-        self.alg.policy.reset = lambda dones=None: None  # feed-forward policy: nothing to reset (play.py:246)
+        self._inference = None
+        if recurrent is not None:  # one stateful callable: `runner.alg.policy.reset(dones)` and the inference policy's `reset` are the same state
+            self._inference = RecurrentInferencePolicy(self.trainer.recurrent.cell_a, self.trainer.actor)
+            self.alg.policy.reset = self._inference.reset
+        else:
+            self.alg.policy.reset = lambda dones=None: None  # feed-forward policy: nothing to reset (play.py:246)
         self.save_interval = int(train_cfg.get("save_interval", 50))
         self.current_learning_iteration = 0
         self.git_status_repos = []
@@ -147,11 +165,15 @@ class OnPolicyRunner:
                 self.alg.load_optimizer_state_dict(d["optimizer_state_dict"])
         elif load_optimizer and d.get("optimizer_state_dict"):
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
+            if self._inference is not None:  # recurrent: the adaptive schedule continues from the checkpoint's rate, so a resumed run repeats the original's steps
+                self.alg.learning_rate = float(self.alg.optimizer.param_groups[0]["lr"])
         self.current_learning_iteration = int(d.get("iter", 0))
         self.trainer.push_parameters()  # (the normalisers' buffers go to their handles with it)
         return d.get("infos")
 
     def get_inference_policy(self, device=None):
+        if self._inference is not None:  # recurrent: the actor's cell (csrc/rl_lstm.hip) and MLP head, stateful, with `reset(dones)`
+            return self._inference
         actor = self.trainer.actor  # the fused HIP inference kernel (csrc/rl_policy.hip), fed by push_parameters()
         norm = (self.trainer.normalizers or (None, None))[0]  # the actor group's statistics are applied, never updated (rsl_rl `act_inference`)
 

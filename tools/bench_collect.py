@@ -5,10 +5,12 @@
 then alg.compute_returns(obs) - every piece on the HIP kernels of this repo (actor + critic: rl_policy.hip, noise /
 log-prob / storage / GAE: rl_rollout.hip, env: rl_env.hip).  Random network weights: the arithmetic does not
 depend on them.
-    python tools/bench_collect.py [task] [num_envs] [iterations] [--obs-history N] [--obs-normalization]
+    python tools/bench_collect.py [task] [num_envs] [iterations] [--obs-history N] [--obs-normalization] [--recurrent]
 --obs-history N: policy-group observation history of N frames, measured against history off in alternating windows of this process.
 --obs-normalization: empirical normalisation of both groups (csrc/rl_obsnorm.hip) against the fused-act loop and against the unfused loop
-(actor + critic, then the act kernel) it is built on, alternating windows of this process."""
+(actor + critic, then the act kernel) it is built on, alternating windows of this process.
+--recurrent: the recurrent loop (two LSTM cells of H = 256 in one launch, csrc/rl_lstm.hip, in front of 128-128-128 heads, unfused act) against the
+feed-forward fused-act loop (512-256-128 networks) and the feed-forward unfused loop, alternating windows of this process."""
 import os
 import sys
 import time
@@ -29,6 +31,9 @@ if "--obs-history" in sys.argv:  # --obs-history N: policy-group observation his
 ap_norm = "--obs-normalization" in sys.argv
 if ap_norm:
     sys.argv.remove("--obs-normalization")
+ap_rec = "--recurrent" in sys.argv
+if ap_rec:
+    sys.argv.remove("--recurrent")
 task = sys.argv[1] if len(sys.argv) > 1 else "RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0"
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 ITERS = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -41,8 +46,9 @@ FUSED_ACT = os.environ.get("RL_FUSED_ACT", "1") == "1"  # sampling / log-prob / 
 OVERLAP = os.environ.get("RL_OVERLAP", "0") == "1"  # the critic of step t on a second stream under env step t (0: actor + critic as one launch in front of act)
 
 
-def setup(hist, norm=False, fused_act=FUSED_ACT):
-    """-> (env, storage, iteration(obs) -> obs) of one collection loop; `hist`: policy-group history length (0: none); `norm`: both groups normalised"""
+def setup(hist, norm=False, fused_act=FUSED_ACT, recurrent=False):
+    """-> (env, storage, iteration(obs) -> obs) of one collection loop; `hist`: policy-group history length (0: none); `norm`: both groups normalised;
+    `recurrent`: LSTM cells of H = 256 in front of 128-128-128 heads (the reference's recurrent agent cfgs)"""
     env = ManagerBasedRLEnv(task, num_envs=N, seed=42, device="cuda:0", obs_history={"policy": hist} if hist else None)
     obs, _ = env.reset()
     od, cd, A = obs["policy"].shape[1], obs["critic"].shape[1], env.num_actions
@@ -52,9 +58,20 @@ def setup(hist, norm=False, fused_act=FUSED_ACT):
         ws = [(rng.standard_normal((dims[i + 1], dims[i])) / np.sqrt(dims[i])).astype(np.float32) for i in range(len(dims) - 1)]
         return MlpPolicy(ws, [np.zeros(d, dtype=np.float32) for d in dims[1:]], "elu", device="cuda:0")
 
-    actor, critic = net([od, 512, 256, 128, A]), net([cd, 512, 256, 128, 1])
+    actor, critic = (net([256, 128, 128, 128, A]), net([256, 128, 128, 128, 1])) if recurrent else (net([od, 512, 256, 128, A]), net([cd, 512, 256, 128, 1]))
     std = torch.ones(A, device="cuda:0")  # init_noise_std = 1.0 (rsl_rl_ppo_cfg.py:16)
     storage = RolloutStorage(N, T, od, cd, A, seed=1, device="cuda:0")
+    if recurrent:
+        from robot_lab_amd.collect import Collector  # noqa: E402
+        from robot_lab_amd.lstm import LstmCell, RecurrentState  # noqa: E402
+
+        def cell(D, H=256):  # nn.LSTM's default initialisation
+            u = lambda *s: rng.uniform(-1 / np.sqrt(H), 1 / np.sqrt(H), s).astype(np.float32)  # noqa: E731
+            return LstmCell(u(4 * H, D), u(4 * H, H), u(4 * H), u(4 * H), device="cuda:0")
+
+        rec = RecurrentState(cell(od), cell(cd), N, T)
+        col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, recurrent=rec)
+        return env, storage, (lambda obs: col.collect()), (actor, critic, col, rec)
     if GRAPH and FUSED and PAIR:
         from robot_lab_amd.collect import Collector  # noqa: E402
 
@@ -158,6 +175,35 @@ if ap_norm:
     count = int(sides["normalized"]["keep"][3][0].get_state()[3])
     ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values()) and count > 0
     print(f"finite: {ok}; rows seen by the policy group's statistics: {count}")
+    sys.exit(0 if ok else 1)
+
+if ap_rec:
+    # feed-forward fused-act loop (the default), feed-forward unfused loop and the recurrent loop, alternating steady-state windows in ONE process
+    ROUNDS = 6
+    kinds = {"fused_act": dict(fused_act=True), "unfused_act": dict(fused_act=False), "recurrent": dict(recurrent=True)}
+    sides = {}
+    with torch.inference_mode():
+        for name, kw in kinds.items():
+            env, storage, iteration, keep = setup(0, **kw)
+            obs = env.get_observations()
+            for _ in range(3):
+                obs = iteration(obs)
+            sides[name] = dict(env=env, storage=storage, iteration=iteration, keep=keep, obs=obs, collect=[])
+        order = list(kinds)
+        for r in range(ROUNDS):
+            for name in (order if r % 2 == 0 else order[::-1]):
+                sd = sides[name]
+                dt, sd["obs"] = window(sd["iteration"], sd["obs"], ITERS)
+                sd["collect"].append(1e6 * dt / ITERS / T)
+    for name, sd in sides.items():
+        v = np.array(sd["collect"])
+        print(f"{task} N={N} {name:12s} collect us/step: windows {np.round(v, 2).tolist()} median {np.median(v):.2f} min {v.min():.2f} max {v.max():.2f}")
+    med = {name: float(np.median(sd["collect"])) for name, sd in sides.items()}
+    print(f"{task} N={N}: the recurrent loop costs {med['recurrent'] - med['fused_act']:+.2f} us/step ({100 * (med['recurrent'] - med['fused_act']) / med['fused_act']:+.1f} %) over the "
+          f"feed-forward fused-act loop, {med['recurrent'] - med['unfused_act']:+.2f} over the feed-forward unfused loop (medians of {ROUNDS} alternating windows)")
+    rec = sides["recurrent"]["keep"][3]
+    ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values()) and bool((rec.h_a != 0).any()) and bool(torch.isfinite(rec.h_c).all())
+    print(f"finite: {ok}")
     sys.exit(0 if ok else 1)
 
 env, storage, iteration, _keep = setup(0)

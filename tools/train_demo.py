@@ -14,8 +14,10 @@ parity test against our own oracle can show.
 `--mirror-loss C` adds rsl_rl's mirror loss with coefficient C on the same tables, `--no-data-augmentation` keeps the mirror loss alone.
 `--obs-normalization` normalises both observation groups; with `--normalize-in-learner` the learners read the raw storage and normalise for
 themselves (`Trainer(normalize_in_learner=True)`), which is what `--symmetry` / `--mirror-loss` need together with it.
+`--recurrent [--rnn-hidden-dim 256]` trains rsl_rl's `ActorCriticRecurrent` (an LSTM in front of 128-128-128 heads, the reference's recurrent agent cfgs):
+the cells run in the captured collection (csrc/rl_lstm.hip), the update is robot_lab_amd/recurrent.py on torch.
     python tools/train_demo.py [--task ID] [--num-envs N] [--iterations K] [--learner torch|hip] [--symmetry lr|fb|lr,fb] [--mirror-loss C]
-                               [--no-data-augmentation] [--obs-normalization [--normalize-in-learner]] [--out DIR]"""
+                               [--no-data-augmentation] [--obs-normalization [--normalize-in-learner]] [--recurrent [--rnn-hidden-dim H]] [--out DIR]"""
 import argparse
 import json
 import os
@@ -43,6 +45,8 @@ def main():
     ap.add_argument("--obs-normalization", action="store_true", help="rsl_rl's empirical normalisation of both observation groups (actor_obs_normalization, critic_obs_normalization)")
     ap.add_argument("--normalize-in-learner", action="store_true",
                     help="with --obs-normalization: the learners normalise the raw stored rows themselves (needed together with --symmetry / --mirror-loss)")
+    ap.add_argument("--recurrent", action="store_true", help="an LSTM in front of 128-128-128 actor / critic heads (Trainer(rnn_type=\"lstm\")); torch learner only")
+    ap.add_argument("--rnn-hidden-dim", type=int, default=256, metavar="H", help="with --recurrent: the LSTM's hidden width")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--save", default=None, metavar="PATH", help="also write a checkpoint in the runner's layout (model_state_dict / optimizer_state_dict / iter / infos): "
@@ -71,7 +75,8 @@ def main():
     print(env, flush=True)  # (names the step kernel: specialised on the task, or the interpreter)
     mirror = dict(mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation) if a.symmetry else {}
     norm = dict(actor_obs_normalization=True, critic_obs_normalization=True, normalize_in_learner=a.normalize_in_learner) if a.obs_normalization else {}
-    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror, **norm)
+    rnn = dict(rnn_type="lstm", rnn_hidden_dim=a.rnn_hidden_dim, actor_hidden=(128, 128, 128), critic_hidden=(128, 128, 128)) if a.recurrent else {}
+    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror, **norm, **rnn)
     print(tr, flush=True)
     # init_at_random_ep_len=True (train.py:224): the first time-outs are spread over an episode length
     env.episode_length_buf = torch.randint(0, env.max_episode_length, (a.num_envs,), generator=torch.Generator().manual_seed(a.seed))
@@ -111,12 +116,12 @@ def main():
                   f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
     wall = time.perf_counter() - t_start
     n_steps = a.iterations * st.num_transitions_per_env * a.num_envs
-    summary = dict(task=a.task, learner=a.learner, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), normalize_in_learner=bool(a.normalize_in_learner), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
+    summary = dict(task=a.task, learner=a.learner, recurrent=bool(a.recurrent), rnn_hidden_dim=a.rnn_hidden_dim if a.recurrent else None, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), normalize_in_learner=bool(a.normalize_in_learner), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
                    collect_ms_per_iteration=1e3 * t_collect / a.iterations, update_ms_per_iteration=1e3 * t_update / a.iterations,
                    first=log[0], last=log[-1])
     print(json.dumps({k: v for k, v in summary.items() if k not in ("first", "last")}))
     os.makedirs(a.out, exist_ok=True)
-    tag = a.task.replace("RobotLab-Isaac-Velocity-", "").replace("-v0", "")
+    tag = a.task.replace("RobotLab-Isaac-Velocity-", "").replace("-v0", "") + ("_recurrent" if a.recurrent else "")
     with open(os.path.join(a.out, f"train_demo_{tag}.json"), "w") as f:
         json.dump(dict(summary=summary, log=log), f, indent=1)
     torch.save(tr.state_dict(), os.path.join(a.out, f"train_demo_{tag}.pt"))
