@@ -566,10 +566,12 @@ struct LbLayout {
 // still share a CU)
 constexpr int CONTACT_WORDS = 9;  // x (3), n (3), bias, d_n, d_t
 constexpr int STASH_SLOT_WORDS = 12;  // ... in the lane scratchpad: three granules
-template <int ROWS, int STASH = 0, bool GRAN = true, bool STASH_GRAN = true>
+constexpr int INERTIA_SLOT_WORDS = 12;  // a rigid-body record (INERTIA_NF = 10 words) in the lane scratchpad: three granules
+template <int ROWS, int STASH = 0, bool GRAN = true, bool STASH_GRAN = true, int INR = 0>
 struct LsLayout {  // word offsets: ROWS sensor rows (timers 4, force history 3, last force 3, friction 3: a granule each, or - word-major - W words) + the contact stash
+  // + INR staged rigid-body records (LsFor::INERTIA_STAGE: behind the stash, whose words the reward stage and the observation rows take over)
   enum { RW = GRAN ? 4 : 3, SSW = STASH_GRAN ? STASH_SLOT_WORDS : CONTACT_WORDS, TIM = 0, HIST = TIM + ROWS * 4, CF = HIST + ROWS * RW, FRIC = CF + ROWS * RW, CT = FRIC + ROWS * RW,
-         WORDS = CT + STASH * SSW };
+         INRT = CT + STASH * SSW, WORDS = INRT + INR * INERTIA_SLOT_WORDS };
 };
 template <class TP, int SUB>
 struct LsFor {  // lane scratchpad layout of an instance
@@ -588,7 +590,22 @@ struct LsFor {  // lane scratchpad layout of an instance
   // the stash as granules (12 instead of 9 words per slot) where four wavefronts of the instance still fit a CU's LDS next to the
   // tables (not the 4-joint quadruped with nine stash slots per lane in the 8-lane mapping: it keeps a word-major stash)
   static constexpr bool STASH_GRAN = GRAN && 4 * (16 * ROWS + STASH_SLOT_WORDS * STASH) * 256 <= 140 * 1024;
-  using type = LsLayout<ROWS, STASH, GRAN, STASH_GRAN>;
+  // The rigid-body records a lane needs in EVERY substep - the link of each of its NIT link groups (link_rigid) and the base link (aba_solve) -
+  // are words of the HBM state tiles that no step changes (the host writes them: mass / COM randomisation at start-up, rl_env_load_state).
+  // Read from the tiles inside the substep loop they are 10 + 10 global loads and two waits per substep of a wavefront that has its SIMD
+  // to itself, the base link's three instructions in front of their use.  Staged: read ONCE per launch at the head of the step
+  // (EnvLane::stage_inertia) into NIT + 1 lane-private records behind the stash, and read back from there in the substeps - three
+  // ds_read_b128 each.  (Not registers: 20 more values live across the elimination, where the quadruped kernels already use all 512.)
+  // Quadrupeds with 16 lanes per env, where the four-wavefront workgroup keeps room for the table image and the observation rows (A1:
+  // 78 -> 102 KB of a CU's 160); the other mappings and the trunk + limbs instances sit at 135 - 155 KB and keep the reloads.
+  // -DRL_INERTIA_RELOAD: the reloads everywhere (analysis builds, tests/test_inertia_stage_emu.py).
+#ifdef RL_INERTIA_RELOAD
+  static constexpr bool INERTIA_STAGE = false;
+#else
+  static constexpr bool INERTIA_STAGE = TP::NW == 0 && SUB == 4 && 4 * (16 * ROWS + STASH_SLOT_WORDS * STASH + INERTIA_SLOT_WORDS * (NIT + 1)) * 256 <= 112 * 1024;
+#endif
+  static constexpr int INR = INERTIA_STAGE ? NIT + 1 : 0;  // records 0 .. NIT - 1: the lane's links; record NIT: the base link
+  using type = LsLayout<ROWS, STASH, GRAN, STASH_GRAN, INR>;
 };
 
 template <class Ctx, class TP, class SP = NoSpec>
@@ -1320,6 +1337,51 @@ struct EnvLane {
     rec.r[3] += rho.l.x; rec.r[4] += rho.l.y; rec.r[5] += rho.l.z;
   }
 
+  // ---- the step-invariant rigid-body records in the lane scratchpad (LsFor::INERTIA_STAGE)
+  // stage_inertia_load(): the loads, at the head of the step behind the early state batch (not inside it: that batch fills the budget of
+  // loads in flight that still count, env_kernel EARLY); stage_inertia_store(): the words into the lane's granules, behind the action
+  // processing - their round trip falls under it.  (The words travel between the two as a value of the caller, EnvProgram::step_front: as
+  // members of the lane object, stored in front of the substep loop, the kernels came out with other multiply-add contractions in the
+  // terminations stage behind the loop - one ulp in the rotation matrix, profiles/inertia_stage_identity.txt.)  Record IT: the link of link
+  // group grp_of(IT), link 0 for a lane without one (link_rigid weighs it with zero mass, as it does the reloaded words); record NIT: the
+  // base link, the same words in all lanes of the env (one address per env: nothing more is fetched than by the lanes of limb 0 alone, and
+  // no EXEC-masked region stands around loads in flight).  Lane-private words: written and read by the same lane, in program order.
+  static constexpr bool INERTIA_STAGE = LsFor<TP, Ctx::SUB>::INERTIA_STAGE;
+  struct InertiaWords {  // (static indices only)
+    float w[INERTIA_STAGE ? LsFor<TP, Ctx::SUB>::INR : 1][INERTIA_NF];
+  };
+  RL_FN float* inertia_words(int r) const { return ctx.template lane_scratch<true>() + (LS::INRT + r * INERTIA_SLOT_WORDS) * LSS; }
+  RL_FN InertiaWords stage_inertia_load() {
+    InertiaWords iw{};
+    if constexpr (INERTIA_STAGE) {
+      static_for<0, NIT>([&](auto it) __attribute__((always_inline)) {
+        const int l = grp_of(it.value) - 1;
+        const uint32_t li = (uint32_t)(LY.LF_INERTIA + ((l >= 0 && l < CL) ? l : 0) * INERTIA_NF);
+#pragma unroll
+        for (int f = 0; f < INERTIA_NF; ++f) iw.w[it.value][f] = LF(li + f);
+      });
+#pragma unroll
+      for (int f = 0; f < INERTIA_NF; ++f) iw.w[NIT][f] = EF(LY.EF_BASE_INERTIA + f);
+    }
+    return iw;
+  }
+  RL_FN void stage_inertia_store(InertiaWords iw) {
+    if constexpr (INERTIA_STAGE) {
+      static_for<0, NIT + 1>([&](auto rc) __attribute__((always_inline)) {
+        const float(&w)[INERTIA_NF] = iw.w[rc.value];
+        float* p = inertia_words(rc.value);
+        st4(p, F4{w[0], w[1], w[2], w[3]});
+        st4(p + 4 * LSS, F4{w[4], w[5], w[6], w[7]});
+        st4(p + 8 * LSS, F4{w[8], w[9], 0.f, 0.f});
+      });
+    }
+  }
+  RL_FN void staged_inertia(int r, float (&w)[INERTIA_NF]) const {
+    const float* p = inertia_words(r);
+    const F4 a = ld4(p), b = ld4(p + 4 * LSS), c = ld4(p + 8 * LSS);
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w; w[8] = c.x; w[9] = c.y;
+  }
+
   // rigid record of the limb link this lane owns in iteration IT (link sub + SUB * IT - 1, if the limb has it)
   template <int IT>
   RL_FN SV link_rigid(const ChainTP& C, const SV V0, const SV (&Vl)[CL], const SV (&al)[CL], LinkRec& rec) const {
@@ -1339,6 +1401,15 @@ struct EnvLane {
       pm += w * C.p(j);
       Vm.a += w * Vl[j].a; Vm.l += w * Vl[j].l;
       am.a += w * al[j].a; am.l += w * al[j].l;
+    }
+    if constexpr (INERTIA_STAGE) {  // the record staged at the head of the step: same words, same arithmetic
+      float w[INERTIA_NF];
+      staged_inertia(IT, w);
+      const float mass = has ? w[0] : 0.f;
+      const V3 cb = pm + mul(Rm, V3{w[1], w[2], w[3]});
+      const SI Im = make_si(mass, cb, rotate(Rm, S3{w[4], w[5], w[6], w[7], w[8], w[9]}));
+      add_rigid(rec, Im, Vm, am, SV{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}});
+      return has ? Vm : V0;
     }
     const uint32_t li = (uint32_t)(LY.LF_INERTIA + (has ? l : 0) * INERTIA_NF);
     const float mass = has ? LF(li) : 0.f;
@@ -1522,6 +1593,10 @@ struct EnvLane {
       }
       rl_pin(jarm); rl_pin(jlo); rl_pin(jhi);
     }
+    // the base link's staged record: read in front of the elimination, used behind it (an LDS read, the same in every lane: no EXEC-masked
+    // region around it, and the recursion covers its latency)
+    float wb[INERTIA_NF] = {};
+    if constexpr (INERTIA_STAGE) staged_inertia(NIT, wb);
     static_for_down<CL - 1>([&](auto jc) {
       constexpr int j = jc.value, gq = j + 1 - G0, so = gq % SUB, io = gq / SUB;  // owner sub-lane / iteration of link group j + 1
 #pragma unroll
@@ -1559,7 +1634,12 @@ struct EnvLane {
 #pragma unroll
       for (int i = 0; i < 6; ++i) P.r[i] += ctx.template leg_bcast<0>(rec[0].r[i]);
     }
-    if (k == 0) {  // the base link itself and the persistent external wrench [UPSTREAM B8]: rides with limb 0
+    if constexpr (INERTIA_STAGE) {
+      if (k == 0) {
+        const SI I0 = make_si(wb[0], V3{wb[1], wb[2], wb[3]}, S3{wb[4], wb[5], wb[6], wb[7], wb[8], wb[9]});
+        add_rigid(P, I0, V0, a0, SV{-(extT + cross(base_com, extF)), -extF});
+      }
+    } else if (k == 0) {  // the base link itself and the persistent external wrench [UPSTREAM B8]: rides with limb 0
       const int bi = LY.EF_BASE_INERTIA;
       const SI I0 = make_si(EF(bi), V3{EF(bi + 1), EF(bi + 2), EF(bi + 3)}, S3{EF(bi + 4), EF(bi + 5), EF(bi + 6), EF(bi + 7), EF(bi + 8), EF(bi + 9)});
       add_rigid(P, I0, V0, a0, SV{-(extT + cross(base_com, extF)), -extF});

@@ -1592,6 +1592,8 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
       this->load();
       load_task();  // same batch of HBM loads as the state: one round trip instead of a second one after the substeps
     }
+    [[maybe_unused]] typename Base::InertiaWords inertia_words;  // the substeps' step-invariant rigid-body records (env_step.h LsFor::INERTIA_STAGE)
+    if constexpr (Base::ABA) inertia_words = this->stage_inertia_load();
     rl_pin(a_in);
     if (log_tl < LOG_PARTS) {
       float* nx = S.log + (size_t)((S.step_counter + 1u) & (uint32_t)(LOG_RING - 1)) * LOG_SLOT_WORDS;
@@ -1615,6 +1617,7 @@ struct EnvProgram : EnvLane<Ctx, TP, SP> {
       q_tgt[j] = L.action_is_vel[j] ? 0.f : pr;
       qd_tgt[j] = L.action_is_vel[j] ? pr : 0.f;
     }
+    if constexpr (Base::ABA) this->stage_inertia_store(inertia_words);  // ... into the lane scratchpad: their round trip fell under the action processing
     // 2 decimation loop: actuators -> physics -> contact sensor
 #ifdef RL_ABL_SUBSTEPS
     if constexpr (Base::ABA) {
