@@ -52,11 +52,12 @@ constexpr int MAXP = 2 * RL_PPO_MAX_LAYERS + 1;
 constexpr float HALF_LOG_2PI = 0.9189385332046727f;
 constexpr int tiles_of(int x) { return (x + TB - 1) / TB; }  // output tiles along an edge of x entries
 
-enum { G_FWD = 0, G_DX = 1, G_DW = 2 };
+enum { G_FWD = 0, G_DX = 1, G_DW = 2, G_DXLIN = 3 };
 
 // C[I][J] = sum_r A(i, r) B(r, j):
 //   G_FWD  i = row, j = output unit, r = input unit:  A = X[row(i)][r],  B = W[j][r];   C = act(. + bias[j])
 //   G_DX   i = row, j = input unit,  r = output unit: A = dZ[i][r],      B = W[r][j];   C = . * elu'(H[i][j])
+//   G_DXLIN  G_DX without the elu' factor: the gradient of a layer's INPUT that no activation produced (csrc/learner/rl_bptt.inl: dL/dh behind the heads)
 //   G_DW   i = output unit, j = input unit, r = row:  A = dZ[r][i],      B = X[row(r)][j]; C = partial[s][i][j] over rows [s chunk, (s + 1) chunk)
 struct GemmProb {
   const float* A;
@@ -1151,3 +1152,6 @@ int rl_ppo_stats_ex(rl_ppo* p, double* out, int32_t n_out, void* stream) {
 
 // the distillation learner (include/rl_distill.h): the same translation unit, so that it launches THESE kernels - nothing is instantiated twice
 #include "learner/rl_distill.inl"
+
+// the recurrent PPO learner (include/rl_bptt.h): the same translation unit again; the step kernels of back-propagation through time are its own
+#include "learner/rl_bptt.inl"

@@ -308,16 +308,22 @@ class NormalizedBatch:
 MAX_INPUT_WIDTH = 512  # = RL_MLP_MAX_WIDTH (include/rl_policy.h) = RL_PPO_MAX_WIDTH (include/rl_ppo.h): widest layer, the input included
 
 
-def check_recurrent_trainer(rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, learner, symmetry, group, normalization, ppo_kw):
+RECURRENT_LEARNERS = ("torch", "hip")
+
+
+def check_recurrent_trainer(rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, learner, symmetry, group, normalization, ppo_kw, recurrent_learner="torch"):
     """What `Trainer(rnn_type=...)` does not combine with is refused with a reason, never ignored (no device needed)."""
     from .recurrent import check_rnn_cfg
 
     check_rnn_cfg("Trainer", rnn_type, rnn_hidden_dim, rnn_num_layers)
     if critic_group not in ("critic", "policy"):
         raise ValueError(f"Trainer: critic_group must be \"critic\" or \"policy\", not {critic_group!r}")
+    if recurrent_learner not in RECURRENT_LEARNERS:
+        raise ValueError(f"Trainer: recurrent_learner must be \"torch\" or \"hip\", not {recurrent_learner!r}")
     if learner == "hip":
-        raise NotImplementedError("Trainer: learner=\"hip\" with a recurrent policy is not implemented: back-propagation through time in the HIP learner is the "
-                                  "follow-up; the recurrent update runs on learner=\"torch\" (robot_lab_amd/recurrent.py), the collection on the HIP cell")
+        raise NotImplementedError("Trainer: learner=\"hip\" with a recurrent policy is not implemented: learner= names the feed-forward learners, and "
+                                  "back-propagation through time in the HIP learner has a switch of its own - pass recurrent_learner=\"hip\" "
+                                  "(robot_lab_amd/recurrent_hip.py) and leave learner= at \"torch\"")
     if learner != "torch":
         raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
     if symmetry is not None or ppo_kw.get("mirror_loss") is not None:
@@ -350,13 +356,15 @@ class Trainer:
     need together with normalised observations; the default stays the scratch matrices of `NormalizedBatch`.
     `rnn_type="lstm"`, `rnn_hidden_dim`, `rnn_num_layers=1`, `critic_group="critic" | "policy"`: a recurrent policy (rsl_rl `ActorCriticRecurrent`; the rule
     is robot_lab_amd/recurrent.py) - `actor_hidden` / `critic_hidden` are then the MLP heads behind the two memories.  The cells run as HIP kernels in
-    the captured collection loop, the update is `recurrent.RecurrentPPO` (torch).  Refused with `learner="hip"`, "gru", several layers, `symmetry`,
-    the normalisation flags and a `group` of more than one rank."""
+    the captured collection loop, the update is `recurrent.RecurrentPPO` (torch) or, with `recurrent_learner="hip"`, `recurrent_hip.HipRecurrentPPO`:
+    back-propagation through time as HIP kernels (include/rl_bptt.h), pushed into cells and heads device to device.  Refused with `learner="hip"`
+    (that keyword names the feed-forward learners), "gru", several layers, `symmetry`, the normalisation flags and a `group` of more than one rank;
+    `recurrent_learner` without `rnn_type` is refused too."""
 
     def __init__(self, env, num_steps_per_env=24, gamma=0.99, lam=0.95, seed=1, use_graph=True, actor_hidden=(512, 256, 128),
                  critic_hidden=(512, 256, 128), init_noise_std=1.0, clip_actions=None, group=None, learner="torch", symmetry=None,
                  actor_obs_normalization=False, critic_obs_normalization=False, normalize_in_learner=False, rnn_type=None, rnn_hidden_dim=256,
-                 rnn_num_layers=1, critic_group="critic", **ppo_kw):
+                 rnn_num_layers=1, critic_group="critic", recurrent_learner="torch", **ppo_kw):
         from .collect import Collector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
@@ -364,7 +372,12 @@ class Trainer:
         self.recurrent = None
         if rnn_type is not None:  # refused before the env is touched: what a recurrent policy does not combine with
             check_recurrent_trainer(rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, learner, symmetry, group,
-                                    actor_obs_normalization or critic_obs_normalization or normalize_in_learner, ppo_kw)
+                                    actor_obs_normalization or critic_obs_normalization or normalize_in_learner, ppo_kw, recurrent_learner)
+        elif recurrent_learner != "torch":
+            if recurrent_learner not in RECURRENT_LEARNERS:
+                raise ValueError(f"Trainer: recurrent_learner must be \"torch\" or \"hip\", not {recurrent_learner!r}")
+            raise NotImplementedError(f"Trainer: recurrent_learner={recurrent_learner!r} is read by a recurrent policy only (rnn_type=\"lstm\"); the learner of a "
+                                      "feed-forward policy is learner=")
         elif critic_group != "critic":
             raise NotImplementedError("Trainer: critic_group is read by a recurrent policy only (rnn_type=\"lstm\"); the feed-forward critic reads the critic group")
         obs, _ = env.reset()
@@ -391,7 +404,7 @@ class Trainer:
         self.env, self.device = env, obs["policy"].device
         if rnn_type is not None:
             self._init_recurrent(env, od, cd, A, num_steps_per_env, gamma, lam, seed, use_graph, actor_hidden, critic_hidden, init_noise_std, clip_actions,
-                                 rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, ppo_kw)
+                                 rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, ppo_kw, recurrent_learner)
             return
         if normalized:
             self.policy = ActorCritic(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std, bool(actor_obs_normalization),
@@ -450,9 +463,10 @@ class Trainer:
         self.iteration = 0
 
     def _init_recurrent(self, env, od, cd, A, num_steps_per_env, gamma, lam, seed, use_graph, actor_hidden, critic_hidden, init_noise_std, clip_actions,
-                        rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, ppo_kw):
-        """`rnn_type="lstm"`: `recurrent.ActorCriticRecurrent` under `recurrent.RecurrentPPO` (torch), the two cells (csrc/rl_lstm.hip) and the MLP heads of
-        input width H in the recurrent `Collector`; all of them are pushed after every update."""
+                        rnn_type, rnn_hidden_dim, rnn_num_layers, critic_group, ppo_kw, recurrent_learner="torch"):
+        """`rnn_type="lstm"`: `recurrent.ActorCriticRecurrent` under `recurrent.RecurrentPPO` (torch) or - `recurrent_learner="hip"` -
+        `recurrent_hip.HipRecurrentPPO` (back-propagation through time as HIP kernels), the two cells (csrc/rl_lstm.hip) and the MLP heads of input
+        width H in the recurrent `Collector`; all of them are pushed after every update."""
         from .collect import Collector
         from .lstm import LstmCell, RecurrentState
         from .policy import MlpPolicy
@@ -461,7 +475,13 @@ class Trainer:
 
         self.policy = ActorCriticRecurrent(od, cd, A, tuple(actor_hidden), tuple(critic_hidden), init_noise_std, rnn_type, rnn_hidden_dim, rnn_num_layers).to(self.device)
         self.normalized, self.normalize_in_learner, self.normalizers, self.symmetry, self.learner = (), False, None, None, "torch"
-        self.alg = RecurrentPPO(self.policy, **ppo_kw)
+        self.recurrent_learner = recurrent_learner
+        if recurrent_learner == "hip":
+            from .recurrent_hip import HipRecurrentPPO
+
+            self.alg = HipRecurrentPPO(self.policy, num_steps=num_steps_per_env, num_envs=env.num_envs, **ppo_kw)
+        else:
+            self.alg = RecurrentPPO(self.policy, **ppo_kw)
         lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
         host = lambda t: t.detach().cpu().numpy()  # noqa: E731
         dev = str(self.device)
@@ -481,7 +501,7 @@ class Trainer:
 
     def __repr__(self):
         sym = f", symmetry={self.symmetry!r}{mirror_repr(self.alg)}" if self.symmetry is not None else ""
-        sym += f", recurrent=lstm({self.policy.rnn_hidden_dim})" if self.recurrent is not None else ""
+        sym += f", recurrent=lstm({self.policy.rnn_hidden_dim}), recurrent_learner={self.recurrent_learner!r}" if self.recurrent is not None else ""
         sym += f", obs_normalization={list(self.normalized)}" if self.normalized else ""
         sym += ", normalize_in_learner=True" if self.normalize_in_learner else ""
         return f"Trainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, iteration={self.iteration}{sym})"
@@ -502,6 +522,8 @@ class Trainer:
         back into the module first."""
         if self.learner == "hip":
             self.alg.store_into(self.policy)
+        if self.recurrent is not None and self.recurrent_learner == "hip":
+            self.alg.sync_policy()
         self.sync_normalizers()
         return self.policy.state_dict()
 
@@ -519,6 +541,9 @@ class Trainer:
             # it follows the push; with Collector(overlap=True) the critic's side stream waits for this stream at the head of every step
             # (collect.py: side.wait_stream(main)), in the capture too.  A collector launched from ANOTHER stream would have to wait for this one.
             self.alg.push(self.actor, self.critic, self.std)
+            return
+        if self.recurrent is not None and self.recurrent_learner == "hip":  # the same ordering: cells, heads and std read the flat buffer in place
+            self.alg.push(self.recurrent.cell_a, self.recurrent.cell_c, self.actor, self.critic, self.std)
             return
         self.actor.load_linear_layers(self.policy.actor)
         self.critic.load_linear_layers(self.policy.critic)
@@ -545,6 +570,7 @@ class Trainer:
         out = dict(mean_reward=float(st.rewards.mean()), done_rate=float(st.dones.float().mean()))
         out.update(self.alg.update(self.update_batch(), self.gen))
         self._push_weights()
-        out["action_std"] = float((self.std if self.learner == "hip" else self.policy.std.detach()).mean())
+        hip = self.learner == "hip" or (self.recurrent is not None and self.recurrent_learner == "hip")
+        out["action_std"] = float((self.std if hip else self.policy.std.detach()).mean())
         self.iteration += 1
         return out

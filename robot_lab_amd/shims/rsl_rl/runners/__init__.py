@@ -11,7 +11,8 @@ environment, the HIP learner of robot_lab_amd/ppo_hip.py, on one GPU or under `-
 `policy.actor_obs_normalization` / `policy.critic_obs_normalization` reach the `Trainer` (csrc/rl_obsnorm.hip); the checkpoint then carries
 rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` buffers.
 A recurrent cfg - `policy.class_name="ActorCriticRecurrent"`, or the reference's `actor=` / `critic=` RNNModel cfgs (robot_lab_amd.recurrent.read_recurrent_cfg) -
-builds `Trainer(rnn_type="lstm", ...)`: the LSTM cells run in the captured collection (csrc/rl_lstm.hip), the update is the torch learner's; checkpoints carry
+builds `Trainer(rnn_type="lstm", ...)`: the LSTM cells run in the captured collection (csrc/rl_lstm.hip), the update is the torch learner's or - with
+`RL_RECURRENT_LEARNER=hip` in the environment - back-propagation through time on the HIP learner of robot_lab_amd/recurrent_hip.py; checkpoints carry
 rsl_rl's `memory_a.rnn.*` / `memory_c.rnn.*` keys, `get_inference_policy()` is stateful with `reset(dones)`."""
 from __future__ import annotations
 
@@ -29,6 +30,15 @@ def learner_from_env(environ=None) -> str:
     return value
 
 
+def recurrent_learner_from_env(environ=None) -> str:
+    """`RL_RECURRENT_LEARNER=torch | hip` (default torch: robot_lab_amd.recurrent.RecurrentPPO), read with a recurrent cfg; anything else is refused"""
+    value = (os.environ if environ is None else environ).get("RL_RECURRENT_LEARNER", "torch")
+    if value not in ("torch", "hip"):
+        raise ValueError(f"RL_RECURRENT_LEARNER={value!r}: the recurrent learner is \"torch\" (robot_lab_amd.recurrent.RecurrentPPO, the default) or \"hip\" "
+                         "(robot_lab_amd.recurrent_hip.HipRecurrentPPO)")
+    return value
+
+
 class OnPolicyRunner:
     def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device: str = "cpu"):
         from robot_lab_amd.ppo import Trainer
@@ -42,8 +52,10 @@ class OnPolicyRunner:
         recurrent = read_recurrent_cfg(train_cfg)
         if recurrent is not None:
             if self.learner == "hip":
-                raise NotImplementedError("stand-in runner: RL_LEARNER=hip with a recurrent cfg is not implemented: back-propagation through time in the HIP "
-                                          "learner is the follow-up; unset RL_LEARNER (the torch learner runs the recurrent update, the HIP cell the collection)")
+                raise NotImplementedError("stand-in runner: RL_LEARNER=hip with a recurrent cfg is not implemented: RL_LEARNER names the feed-forward learners, "
+                                          "and back-propagation through time in the HIP learner has a switch of its own - unset RL_LEARNER and set "
+                                          "RL_RECURRENT_LEARNER=hip (robot_lab_amd/recurrent_hip.py)")
+            recurrent["recurrent_learner"] = recurrent_learner_from_env()
             pol = dict(class_name="ActorCritic", actor_hidden_dims=recurrent.pop("actor_hidden"), critic_hidden_dims=recurrent.pop("critic_hidden"),
                        init_noise_std=recurrent.pop("init_noise_std"), noise_std_type=pol.get("noise_std_type", "scalar"))
         if pol.get("class_name", "ActorCritic") != "ActorCritic" or alg.get("class_name", "PPO") != "PPO":
@@ -87,6 +99,8 @@ class OnPolicyRunner:
                                clip_actions=getattr(env, "clip_actions", None), group=self.group if self.group.enabled else None, learner=self.learner,
                                **{k: v for k, v in norm.items() if v}, **(recurrent or {}), **{k: alg[k] for k in keys if k in alg})
         self.alg = self.trainer.alg
+        # the learner keeps master parameters and Adam's state on the device (HipPPO, or - RL_RECURRENT_LEARNER=hip - HipRecurrentPPO: the same methods)
+        self._device_learner = self.learner == "hip" or (recurrent is not None and recurrent.get("recurrent_learner") == "hip")
         self._inference = None
         if recurrent is not None:  # one stateful callable: `runner.alg.policy.reset(dones)` and the inference policy's `reset` are the same state
             self._inference = RecurrentInferencePolicy(self.trainer.recurrent.cell_a, self.trainer.actor)
@@ -143,11 +157,11 @@ class OnPolicyRunner:
             self._log_in_flight = None
         if self.log_dir and main:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
-        if self.learner == "hip":
+        if self._device_learner:
             self.alg.store_into(self.alg.policy)  # `runner.alg.policy` is current after learn(), as the torch learner's is (exporters, play.py)
 
     def save(self, path: str, infos=None):
-        if self.learner == "hip":  # the master parameters and Adam's state live on the device: into the module / torch.optim.Adam's layout
+        if self._device_learner:  # the master parameters and Adam's state live on the device: into the module / torch.optim.Adam's layout
             self.alg.store_into(self.alg.policy)
             optimizer_state = self.alg.optimizer_state_dict()
         else:
@@ -159,7 +173,7 @@ class OnPolicyRunner:
     def load(self, path: str, load_optimizer: bool = True, map_location=None):
         d = torch.load(path, map_location=map_location or self.trainer.device, weights_only=False)
         self.alg.policy.load_state_dict(d["model_state_dict"])  # strict: normaliser keys the flags do not ask for - or miss - raise here
-        if self.learner == "hip":
+        if self._device_learner:
             self.alg.load_from(self.alg.policy)
             if load_optimizer and d.get("optimizer_state_dict"):
                 self.alg.load_optimizer_state_dict(d["optimizer_state_dict"])

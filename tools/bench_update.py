@@ -28,8 +28,11 @@ issues every mini-batch through Python instead of running ahead inside one libra
 learners read its matrices; "learner" (`normalize_in_learner=True`): the learners read the raw storage - torch through the modules' forward, HIP
 in its first layer's operand fetch (`HipPPO(obs_normalizers=...)`).  "scratch" is timed with symmetry "off" only: mirroring rows that were
 normalised before is not the rule, and the Trainer refuses it.
+`--recurrent [--rnn-hidden-dim H]`: the recurrent update (LSTM of H = 256 in front of 128-128-128 heads, 5 epochs x 4 blocks of whole trajectories) on one
+batch collected by the recurrent collector: `recurrent.RecurrentPPO.update` (torch autograd through time) against `recurrent_hip.HipRecurrentPPO.update`
+(csrc/learner/rl_bptt.inl), the same alternation; the FLOPs are those of the recurrence, its backward and the heads.  The other switches do not apply.
     python tools/bench_update.py [--task ID ...] [--num-envs N ...] [--repeat R] [--warmup W] [--symmetry off|lr|fb|lr,fb ...] [--mirror-loss C] [--split]
-                                 [--obs-normalization scratch|learner]"""
+                                 [--obs-normalization scratch|learner] [--recurrent [--rnn-hidden-dim H]]"""
 import argparse
 import copy
 import json
@@ -152,6 +155,51 @@ def bench_one(tr, tab, repeat, warmup, seed, split=False, **kw):
     return res
 
 
+def recurrent_flops(alg, rows: int) -> float:
+    """2 flops per multiply-add x rows x epochs x (the memories: W_ih forward + dW, W_hh forward + dX + dW; the heads: forward + dX + dW per layer - the
+    first layer's dX is dL/dh)"""
+    H4 = 4 * alg.hidden
+    macs = sum(H4 * D * 2 + H4 * alg.hidden * 3 for D in (alg.obs_dim, alg.critic_obs_dim))
+    macs += sum(dims[l] * dims[l + 1] * 3 for dims in (alg.actor_dims, alg.critic_dims) for l in range(len(dims) - 1))
+    return 2.0 * macs * rows * alg.num_learning_epochs
+
+
+def bench_recurrent(task, num_envs, repeat, warmup, hidden=256, seed=42):
+    from robot_lab_amd.recurrent import RecurrentPPO
+    from robot_lab_amd.recurrent_hip import HipRecurrentPPO
+
+    env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
+    tr = Trainer(env, seed=seed, rnn_type="lstm", rnn_hidden_dim=hidden, actor_hidden=(128, 128, 128), critic_hidden=(128, 128, 128))
+    env.episode_length_buf = torch.randint(0, int(env.max_episode_length), (num_envs,), generator=torch.Generator().manual_seed(seed))  # dones inside the window
+    tr.collector.collect()
+    torch.cuda.synchronize()
+    batch, st = tr.update_batch(), tr.storage
+    learners = {"torch": RecurrentPPO(copy.deepcopy(tr.policy)), "hip": HipRecurrentPPO(copy.deepcopy(tr.policy))}
+    times = {k: [] for k in learners}
+    for it in range(warmup + repeat):
+        for k, alg in learners.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            out = alg.update(batch)
+            t1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                times[k].append(t0.elapsed_time(t1))
+            assert all(v == v for v in out.values()), (k, out)  # no NaN
+    rows = st.num_transitions_per_env * (num_envs // learners["hip"].num_mini_batches) * learners["hip"].num_mini_batches
+    flops = recurrent_flops(learners["hip"], rows)
+    res = dict(task=task, num_envs=num_envs, recurrent=f"lstm({hidden})", rows=rows, done_rate=float(st.dones.float().mean()), repeat=repeat, warmup=warmup,
+               update_gflop=flops / 1e9)
+    for k, t in times.items():
+        med = statistics.median(t)
+        res[k] = dict(median_ms=med, min_ms=min(t), max_ms=max(t), tflops_at_median=flops / med / 1e9)
+    res["speedup_median"] = res["torch"]["median_ms"] / res["hip"]["median_ms"]
+    learners["hip"].close()
+    tr.recurrent.close(); env.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", nargs="+", default=["RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0", "RobotLab-Isaac-Velocity-Rough-Unitree-G1-v0"])
@@ -163,7 +211,17 @@ def main():
     ap.add_argument("--split", action="store_true", help="also time the begin / local / apply sequence of a multi-GPU run at a world of one")
     ap.add_argument("--obs-normalization", choices=("scratch", "learner"), default=None,
                     help="normalise both observation groups: in a pass before every update (scratch) or inside the learners (learner)")
+    ap.add_argument("--recurrent", action="store_true", help="time the recurrent update: the torch rule against the HIP learner's back-propagation through time")
+    ap.add_argument("--rnn-hidden-dim", type=int, default=256)
     a = ap.parse_args()
+    if a.recurrent:
+        if a.symmetry != ["off"] or a.mirror_loss is not None or a.split or a.obs_normalization:
+            ap.error("--recurrent does not combine with --symmetry, --mirror-loss, --split or --obs-normalization (the recurrent learners refuse them)")
+        if len(a.num_envs) != len(a.task):
+            ap.error("one --num-envs per --task")
+        for task, n in zip(a.task, a.num_envs):
+            print(json.dumps(bench_recurrent(task, n, a.repeat, a.warmup, a.rnn_hidden_dim)), flush=True)
+        return
     for spec in a.symmetry:
         if spec != "off":
             parse_mirrors(spec)
