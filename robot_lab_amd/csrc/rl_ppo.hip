@@ -1155,3 +1155,7 @@ int rl_ppo_stats_ex(rl_ppo* p, double* out, int32_t n_out, void* stream) {
 
 // the recurrent PPO learner (include/rl_bptt.h): the same translation unit again; the step kernels of back-propagation through time are its own
 #include "learner/rl_bptt.inl"
+
+// the recurrent distillation learner (include/rl_distill_bptt.h): behind both, since it launches the distillation learner's head and the recurrent
+// learner's step kernels
+#include "learner/rl_distill_bptt.inl"

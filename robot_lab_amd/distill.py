@@ -158,16 +158,32 @@ class DistillTrainer:
     `learner="torch"`: `Distillation` above; `learner="hip"`: `distill_hip.HipDistillation`, the same rule as HIP kernels.
     `student_group` / `teacher_group`: which of the env's observation groups ("policy" | "critic") each network reads.
     `teacher_obs_normalization`: the teacher was trained behind an `actor_obs_normalizer`; its statistics come with the teacher's
-    checkpoint, are applied in front of the teacher and never updated.  The teacher arrives through `load_state_dict` / `load_teacher`."""
+    checkpoint, are applied in front of the teacher and never updated.  The teacher arrives through `load_state_dict` / `load_teacher`.
+    `rnn_type="lstm"` (with `rnn_hidden_dim`, `rnn_num_layers=1`): a recurrent student, robot_lab_amd/distill_recurrent.py - `StudentTeacherRecurrent`,
+    `RecurrentDistillation` or `distill_recurrent_hip.HipRecurrentDistillation`, `RecurrentDistillCollector`.  `teacher_recurrent` (None: as the
+    student): the teacher has a memory of its own (a recurrent PPO checkpoint) or is feed-forward.  `carry_learner_state`: after an update the
+    collection's student state becomes the learner's `final_state`; False: the collection continues from its own cells."""
 
     def __init__(self, env, num_steps_per_env=120, student_hidden=(128, 128, 128), teacher_hidden=(512, 256, 128), init_noise_std=0.1, learner="torch",
-                 student_group="policy", teacher_group="policy", teacher_obs_normalization=False, clip_actions=None, seed=1, use_graph=True, **distillation_kw):
+                 student_group="policy", teacher_group="policy", teacher_obs_normalization=False, clip_actions=None, seed=1, use_graph=True,
+                 rnn_type=None, rnn_hidden_dim=256, rnn_num_layers=1, teacher_recurrent=None, carry_learner_state=True, **distillation_kw):
         from .distill_collect import DistillCollector
         from .policy import MlpPolicy
         from .rollout import RolloutStorage
 
         if learner not in ("torch", "hip"):
             raise ValueError(f"learner must be \"torch\" or \"hip\", not {learner!r}")
+        self.recurrent = rnn_type is not None
+        if self.recurrent:  # (refused before the env is touched)
+            from .recurrent import check_rnn_cfg
+
+            check_rnn_cfg("DistillTrainer", rnn_type, rnn_hidden_dim, rnn_num_layers)
+            teacher_recurrent = True if teacher_recurrent is None else bool(teacher_recurrent)
+        elif teacher_recurrent:
+            raise NotImplementedError("DistillTrainer: teacher_recurrent=True without rnn_type= means a feed-forward student with a recurrent teacher, which is "
+                                      "not implemented (out of scope: the collection runs the teacher's memory next to the student's); pass rnn_type=\"lstm\" "
+                                      "for a recurrent student, or teacher_recurrent=False with a feed-forward PPO checkpoint")
+        self.teacher_recurrent, self.carry_learner_state = bool(teacher_recurrent), bool(carry_learner_state)
         obs, _ = env.reset()
         for role, g in (("student", student_group), ("teacher", teacher_group)):
             if g not in obs:
@@ -179,6 +195,10 @@ class DistillTrainer:
         torch.manual_seed(seed)
         self.env, self.device, self.learner = env, obs[student_group].device, learner
         self.student_group, self.teacher_group = student_group, teacher_group
+        if self.recurrent:
+            self._init_recurrent(env, sd, td, A, num_steps_per_env, tuple(student_hidden), tuple(teacher_hidden), init_noise_std, teacher_obs_normalization,
+                                 clip_actions, seed, use_graph, int(rnn_hidden_dim), distillation_kw)
+            return
         self.policy = StudentTeacher(sd, td, A, tuple(student_hidden), tuple(teacher_hidden), init_noise_std, teacher_obs_normalization).to(self.device)
         if learner == "hip":
             from .distill_hip import HipDistillation
@@ -203,6 +223,62 @@ class DistillTrainer:
         self.batch = types.SimpleNamespace(observations=self.storage.observations, teacher_actions=self.collector.teacher_actions)
         self.iteration = 0
 
+    def _init_recurrent(self, env, sd, td, A, num_steps_per_env, student_hidden, teacher_hidden, init_noise_std, teacher_obs_normalization, clip_actions, seed,
+                        use_graph, H, distillation_kw):
+        """the recurrent student's half of the constructor: memories in front of both MLPs (the teacher's only with `teacher_recurrent`)"""
+        from .distill_collect import RecurrentDistillCollector
+        from .distill_recurrent import RecurrentDistillation, StudentTeacherRecurrent
+        from .lstm import LstmCell
+        from .policy import MlpPolicy
+        from .rollout import RolloutStorage
+
+        dev = str(self.device)
+        self.policy = StudentTeacherRecurrent(sd, td, A, student_hidden, teacher_hidden, init_noise_std, rnn_hidden_dim=H, teacher_recurrent=self.teacher_recurrent,
+                                              teacher_obs_normalization=teacher_obs_normalization).to(self.device)
+        if self.learner == "hip":
+            from .distill_recurrent_hip import HipRecurrentDistillation
+
+            self.alg = HipRecurrentDistillation(self.policy, num_envs=env.num_envs, **distillation_kw)
+        else:
+            self.alg = RecurrentDistillation(self.policy, **distillation_kw)
+        lin = lambda m: [x for x in m if isinstance(x, nn.Linear)]  # noqa: E731
+        host = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        self.student = MlpPolicy([host(x.weight) for x in lin(self.policy.student)], [host(x.bias) for x in lin(self.policy.student)], "elu", device=dev)
+        self.teacher = MlpPolicy([host(x.weight) for x in lin(self.policy.teacher)], [host(x.bias) for x in lin(self.policy.teacher)], "elu", device=dev)
+        self.cell_s = LstmCell.from_module(self.policy.memory_s.rnn, device=dev)
+        self.cell_t = LstmCell.from_module(self.policy.memory_t.rnn, device=dev) if self.teacher_recurrent else None
+        self.normalizer = None
+        if teacher_obs_normalization:
+            from .obsnorm import ObsNormalizer
+
+            m = self.policy.teacher_obs_normalizer
+            self.normalizer = ObsNormalizer(m._mean.shape[1], m.eps, max_rows=env.num_envs, device=dev)
+        self.storage = RolloutStorage(env.num_envs, num_steps_per_env, sd, td, A, seed=seed, device=dev)
+        self.std = self.policy.std.detach().clone()
+        self.collector = RecurrentDistillCollector(env, self.student, self.teacher, self.storage, self.std, self.cell_s, self.cell_t, student_group=self.student_group,
+                                                   teacher_group=self.teacher_group, normalizer=self.normalizer, use_graph=use_graph, clip_actions=clip_actions)
+        self.batch = types.SimpleNamespace(observations=self.storage.observations, teacher_actions=self.collector.teacher_actions, dones=self.storage.dones,
+                                           h0=self.collector.h0, c0=self.collector.c0)
+        self.iteration = 0
+
+    def inference_policy(self):
+        """the student as `runner.get_inference_policy()` hands it out: the MLP kernel, or for a recurrent student the stateful callable with
+        `reset(dones)` on a cell and a head of its own (playing does not disturb the collection's state or the captured loop's buffers); a
+        snapshot of the student at the time of the call"""
+        if not self.recurrent:
+            return self.student
+        from .distill_recurrent import RecurrentStudentInferencePolicy
+        from .lstm import LstmCell
+
+        from .policy import MlpPolicy
+
+        if self.learner == "hip":
+            self.alg.store_into(self.policy)
+        lin = [x for x in self.policy.student if isinstance(x, nn.Linear)]
+        host = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        head = MlpPolicy([host(x.weight) for x in lin], [host(x.bias) for x in lin], "elu", device=str(self.device))  # (its own output buffer: any row count)
+        return RecurrentStudentInferencePolicy(LstmCell.from_module(self.policy.memory_s.rnn, device=str(self.device)), head, self.student_group)
+
     def __repr__(self):
         return (f"DistillTrainer(learner={self.learner!r}, alg={type(self.alg).__name__}, num_envs={self.env.num_envs}, student<-{self.student_group!r}, "
                 f"teacher<-{self.teacher_group!r}, iteration={self.iteration})")
@@ -215,6 +291,10 @@ class DistillTrainer:
             self.alg.load_from(self.policy)
         self.student.load_linear_layers(self.policy.student)
         self.teacher.load_linear_layers(self.policy.teacher)
+        if self.recurrent:
+            self.cell_s.load_module(self.policy.memory_s.rnn)
+            if self.cell_t is not None:
+                self.cell_t.load_module(self.policy.memory_t.rnn)
         if self.normalizer is not None:
             self.normalizer.load_module(self.policy.teacher_obs_normalizer)
         self.std.copy_(self.policy.std.detach())
@@ -226,7 +306,15 @@ class DistillTrainer:
         return self.policy.state_dict()
 
     def _push(self):
-        if self.learner == "hip":
+        if self.recurrent:
+            if self.learner == "hip":
+                self.alg.push(self.cell_s, self.student)
+            else:
+                self.cell_s.load_module(self.policy.memory_s.rnn)
+                self.student.load_linear_layers(self.policy.student)
+            if self.carry_learner_state:  # what rsl_rl's `last_hidden_states` is believed to do; the reset mask of the next step 0 stays dones[T - 1]
+                self.collector.set_student_state(*self.alg.final_state)
+        elif self.learner == "hip":
             self.alg.push(self.student)  # device to device on the current stream; the next collection follows it on the same stream
         else:
             self.student.load_linear_layers(self.policy.student)

@@ -10,7 +10,11 @@
 The `RolloutStorage` holds the student's rows (observations), the teacher's rows (its critic slot, RAW), actions, rewards and dones; its value
 slot is zero, so the env kernel's time-out bootstrap adds nothing.  With a `normalizer` (the teacher's `actor_obs_normalizer` of its PPO run) one
 `apply` runs in front of the teacher; the statistics are never updated.  Captured under `Collector`'s conditions (T even); a replay equals
-the eager loop bit for bit (tests/test_gpu_distill.py)."""
+the eager loop bit for bit (tests/test_gpu_distill.py).
+
+`RecurrentDistillCollector` is the same loop for a recurrent student (robot_lab_amd/distill_recurrent.py): two memories in front of the two MLPs,
+ONE `rl_lstm_step_pair` per step for the student's and the teacher's cell (one `rl_lstm_step` for the student with a feed-forward teacher), the
+reset mask the done bytes of storage slot t - 1, and only step 0 saves the student's (h~, c~): the update's `h0` / `c0`."""
 from __future__ import annotations
 
 import torch
@@ -79,3 +83,61 @@ class DistillCollector:
         self._graph.replay()
         self.obs = self.env.get_observations()
         return self.obs
+
+
+class RecurrentDistillCollector(DistillCollector):
+    """`DistillCollector` with memories (csrc/rl_lstm.hip, robot_lab_amd/lstm.py `LstmCell`): `cell_s` in front of `student`, `cell_t` in front of
+    `teacher` or None for a feed-forward teacher, which reads its raw (optionally normalised) rows as before.  Per step: the cell launch - the reset of
+    the previous step's dones applied, read from storage slot t - 1 without a launch of their own (step 0 reads `reset`, which takes the last slot
+    once per iteration) -, the two MLPs in one launch on the student's h' and the teacher's h' (or rows), the unfused act, env.step.  `h0` / `c0`
+    [N, H]: the student state step 0 saw, its own reset applied.  The state lives in two ping-pong buffers; T even brings a captured loop back to
+    the buffers it started from."""
+
+    def __init__(self, env, student, teacher, storage, action_std, cell_s, cell_t=None, **kw):
+        super().__init__(env, student, teacher, storage, action_std, **kw)
+        N, dev, H = env.num_envs, storage.device, cell_s.hidden
+        if student.in_dim != H or (cell_t is not None and teacher.in_dim != cell_t.hidden):
+            raise ValueError(f"RecurrentDistillCollector: the MLPs read rows of {student.in_dim} / {teacher.in_dim} columns, the memories produce {H}" +
+                             (f" / {cell_t.hidden}" if cell_t is not None else ""))
+        self.cell_s, self.cell_t = cell_s, cell_t
+        z = lambda n: torch.zeros(N, n, device=dev, dtype=torch.float32)  # noqa: E731
+        self._hs, self._cs = (z(H), z(H)), (z(H), z(H))
+        if cell_t is not None:
+            self._ht, self._ct = (z(cell_t.hidden), z(cell_t.hidden)), (z(cell_t.hidden), z(cell_t.hidden))
+        self._k = 0  # which of the two buffers holds the current state
+        self.h0, self.c0 = z(H), z(H)
+        self.reset = torch.zeros(N, dtype=torch.uint8, device=dev)
+
+    def student_state(self):
+        """(h, c) of the student as the next step will read them (before its reset)"""
+        return self._hs[self._k], self._cs[self._k]
+
+    def set_student_state(self, h, c):
+        """the learner's final state becomes the collection's (stream-ordered copies into the buffers the next step reads)"""
+        self._hs[self._k].copy_(h)
+        self._cs[self._k].copy_(c)
+
+    def _iteration(self, obs):
+        st, env = self.storage, self.env
+        st.clear()
+        dones = st.dones.view(torch.uint8)
+        for t in range(self.T):
+            s_rows, t_rows = obs[self.student_group], obs[self.teacher_group]
+            seen = t_rows if self.normalizer is None else self.normalizer.apply(t_rows, out=self._norm_rows)
+            k = self._k
+            reset = self.reset if t == 0 else dones[t - 1]
+            saved = dict(h_saved=self.h0, c_saved=self.c0) if t == 0 else {}
+            if self.cell_t is not None:
+                self.cell_s.step_pair(s_rows, self._hs[k], self._cs[k], self._hs[1 - k], self._cs[1 - k], self.cell_t, seen, self._ht[k], self._ct[k],
+                                      self._ht[1 - k], self._ct[1 - k], reset=reset, **saved)
+                seen = self._ht[1 - k]
+            else:
+                self.cell_s.step(s_rows, self._hs[k], self._cs[k], self._hs[1 - k], self._cs[1 - k], reset=reset, **saved)
+            self._k = 1 - k
+            mean, _ = self.student.forward_pair(self._hs[1 - k], self.teacher, seen, other_out=self.teacher_actions[t])
+            actions = st.act(s_rows, t_rows, mean, self.std, self._zero_values)
+            if self.clip_actions is not None:
+                actions = actions.clamp(-self.clip_actions, self.clip_actions)
+            obs, _, _, _, _ = env.step(actions, rollout=st, gamma=self.gamma)
+        self.reset.copy_(dones[self.T - 1])
+        return obs

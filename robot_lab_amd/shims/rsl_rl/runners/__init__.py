@@ -258,11 +258,57 @@ def read_distillation_cfg(train_cfg: dict, env_groups=("policy", "critic")) -> d
     return kw
 
 
+def _is_rnn_model(m) -> bool:
+    return isinstance(m, dict) and (_given(m, "rnn_type") is not None or m.get("class_name") == "RNNModel")
+
+
+def is_recurrent_distillation_cfg(train_cfg: dict) -> bool:
+    """whether a distillation runner cfg asks for a recurrent student or teacher (`RslRlRNNModelCfg`).  Pure."""
+    return any(_is_rnn_model(_given(train_cfg, role)) for role in ("student", "teacher"))
+
+
+def read_recurrent_distillation_cfg(train_cfg: dict, env_groups=("policy", "critic")) -> dict:
+    """The keywords of `robot_lab_amd.distill.DistillTrainer` from the reference's recurrent distillation cfg
+    (`AnymalDFlatDistillationRunnerRecurrentCfg.to_dict()`): the student an RNNModel, the teacher an RNNModel with equal rnn settings or an MLPModel.
+    Every other refusal is `read_distillation_cfg`'s, which reads the cfg with the rnn fields taken out.  Pure (no device, no env)."""
+    from robot_lab_amd.recurrent import check_rnn_cfg
+
+    models = {role: _given(train_cfg, role) for role in ("student", "teacher")}
+    for role, m in models.items():
+        if not isinstance(m, dict):
+            raise ValueError(f"stand-in DistillationRunner: the cfg has no `{role}` model cfg (RslRlRNNModelCfg / RslRlMLPModelCfg)")
+    if not _is_rnn_model(models["student"]):
+        raise NotImplementedError("stand-in DistillationRunner: the teacher is a recurrent model and the student is not: a feed-forward student with a recurrent "
+                                  "teacher is not implemented (out of scope) - make the student an RslRlRNNModelCfg too, or distil a feed-forward teacher")
+    rnn = {}
+    for role, m in models.items():
+        if not _is_rnn_model(m):
+            continue
+        if m.get("class_name", "RNNModel") != "RNNModel" or _given(m, "rnn_type") is None:
+            raise NotImplementedError(f"stand-in DistillationRunner: the {role} is {m.get('class_name')!r} with rnn_type={m.get('rnn_type')!r}: a recurrent model is "
+                                      "class_name=\"RNNModel\" with an rnn_type")
+        rnn[role] = (_given(m, "rnn_type"), int(_given(m, "rnn_hidden_dim", 256)), int(_given(m, "rnn_num_layers", 1)))
+        check_rnn_cfg(f"stand-in DistillationRunner ({role})", *rnn[role])
+    if "teacher" in rnn and rnn["teacher"] != rnn["student"]:
+        raise NotImplementedError(f"stand-in DistillationRunner: student and teacher rnn settings differ ({rnn['student']} / {rnn['teacher']}): "
+                                  "StudentTeacherRecurrent has one rnn_type / rnn_hidden_dim / rnn_num_layers for both memories")
+    plain = dict(train_cfg)
+    for role, m in models.items():  # the feed-forward reader sees MLP models: its refusals (activation, normalisation, algorithm, optimiser, groups) apply unchanged
+        plain[role] = {k: v for k, v in m.items() if k not in ("rnn_type", "rnn_hidden_dim", "rnn_num_layers")}
+        if plain[role].get("class_name") == "RNNModel":
+            plain[role]["class_name"] = "MLPModel"
+    kw = read_distillation_cfg(plain, env_groups)
+    kw.update(rnn_type=rnn["student"][0], rnn_hidden_dim=rnn["student"][1], rnn_num_layers=rnn["student"][2], teacher_recurrent="teacher" in rnn)
+    return kw
+
+
 class DistillationRunner:
     """rsl_rl's `DistillationRunner` as the reference's scripts use it (train.py:205-217): the same calls as `OnPolicyRunner`.  Collection is
     robot_lab_amd/distill_collect.py (student and teacher in one launch, one hipGraph launch per iteration), the update robot_lab_amd/distill.py
     or - `RL_LEARNER=hip` - robot_lab_amd/distill_hip.py.  `load(path)` goes through `StudentTeacher.load_state_dict`: a PPO checkpoint becomes the
-    teacher (iteration 0, fresh optimiser), a distillation checkpoint resumes iteration and optimiser.  Checkpoints are `model_<it>.pt` in rsl_rl's layout."""
+    teacher (iteration 0, fresh optimiser), a distillation checkpoint resumes iteration and optimiser.  Checkpoints are `model_<it>.pt` in rsl_rl's layout.
+    A cfg with RNNModel networks (`is_recurrent_distillation_cfg`) gives the recurrent student of robot_lab_amd/distill_recurrent.py: the same calls,
+    `load()` of a recurrent PPO checkpoint gives the teacher, `get_inference_policy()` the stateful callable with `reset(dones)`."""
 
     def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device: str = "cpu"):
         from robot_lab_amd.dist import LearnerGroup, rank_info
@@ -275,7 +321,8 @@ class DistillationRunner:
         self.env, self.cfg, self.log_dir, self.device = env, train_cfg, log_dir, device
         self.learner = learner_from_env()
         inner = env.unwrapped
-        kw = read_distillation_cfg(train_cfg, tuple(inner.get_observations().keys()))
+        self.recurrent = is_recurrent_distillation_cfg(train_cfg)
+        kw = (read_recurrent_distillation_cfg if self.recurrent else read_distillation_cfg)(train_cfg, tuple(inner.get_observations().keys()))
         self.group = LearnerGroup(device)  # (a world of one: disabled, no process group)
         self.trainer = DistillTrainer(inner, learner=self.learner, clip_actions=_given(train_cfg, "clip_actions", getattr(env, "clip_actions", None)), **kw)
         self.alg = self.trainer.alg
@@ -335,6 +382,8 @@ class DistillationRunner:
         return d.get("infos")
 
     def get_inference_policy(self, device=None):
+        if self.recurrent:  # stateful: policy(obs) advances the student's memory, policy.reset(dones) zeroes rows (play.py calls it after env.step)
+            return self.trainer.inference_policy()
         student = self.trainer.student  # the fused HIP inference kernel, fed by the push after every update
 
         def policy(obs):

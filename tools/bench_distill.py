@@ -10,7 +10,10 @@ the teacher is a randomly initialised 512-256-128 actor.  The batch is collected
 torch, hip, ...) with device events around each `update()` - which ends in the learner's own read-back of the statistics - after `--warmup`
 untimed updates of each.  The collection is timed the same way: `--repeat` iterations of the eager loop and of the captured replay, alternating.
 Medians, minima and maxima in ms; one JSON line, and a text report to `--out`.
-    python tools/bench_distill.py [--task ID] [--num-envs N] [--steps T] [--repeat R] [--warmup W] [--out FILE]"""
+`--recurrent`: the reference's recurrent cfg instead - an LSTM of 256 in front of student and teacher (128-128-128 each; `--mlp-teacher`: a
+feed-forward 512-256-128 teacher), `RecurrentDistillation` against `HipRecurrentDistillation` (csrc/learner/rl_distill_bptt.inl), the collection
+with the two memories.
+    python tools/bench_distill.py [--recurrent [--mlp-teacher]] [--task ID] [--num-envs N] [--steps T] [--repeat R] [--warmup W] [--out FILE]"""
 import argparse
 import copy
 import json
@@ -48,16 +51,28 @@ def main():
     ap.add_argument("--repeat", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--recurrent", action="store_true", help="an LSTM student (and teacher): robot_lab_amd/distill_recurrent.py")
+    ap.add_argument("--mlp-teacher", action="store_true", help="with --recurrent: a feed-forward teacher")
     a = ap.parse_args()
+    if a.mlp_teacher and not a.recurrent:
+        ap.error("--mlp-teacher goes with --recurrent")
     kw = dict(num_learning_epochs=2, gradient_length=15, learning_rate=1e-3)
+    rnn_teacher = a.recurrent and not a.mlp_teacher
+    teacher_hidden = (128, 128, 128) if rnn_teacher else (512, 256, 128)
+    rkw = dict(rnn_type="lstm", rnn_hidden_dim=256, teacher_recurrent=rnn_teacher) if a.recurrent else {}
     trainers = {}
     for graph in (False, True):  # two envs with the same seed: the eager loop and the captured one
         env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=1, device="cuda:0")
-        tr = DistillTrainer(env, num_steps_per_env=a.steps, student_hidden=(128, 128, 128), teacher_hidden=(512, 256, 128), init_noise_std=0.1, learner="torch",
-                            use_graph=graph, seed=1, **kw)
+        tr = DistillTrainer(env, num_steps_per_env=a.steps, student_hidden=(128, 128, 128), teacher_hidden=teacher_hidden, init_noise_std=0.1, learner="torch",
+                            use_graph=graph, seed=1, **rkw, **kw)
         torch.manual_seed(2)
         od = env.get_observations()["policy"].shape[1]
-        tr.load_state_dict(ActorCritic(od, od, env.num_actions).state_dict())
+        if rnn_teacher:
+            from robot_lab_amd.recurrent import ActorCriticRecurrent
+
+            tr.load_state_dict(ActorCriticRecurrent(od, od, env.num_actions).state_dict())
+        else:
+            tr.load_state_dict(ActorCritic(od, od, env.num_actions, actor_hidden=teacher_hidden).state_dict())
         trainers[graph] = tr
     for _ in range(max(a.warmup, 2)):  # (the captured side: eager warm-up, then capture + replay)
         for tr in trainers.values():
@@ -69,7 +84,13 @@ def main():
             collect[graph].append(timed(tr.collector.collect))
     tr = trainers[True]
     batch = tr.batch
-    learners = dict(torch=Distillation(copy.deepcopy(tr.policy), **kw), hip=HipDistillation(copy.deepcopy(tr.policy), num_envs=a.num_envs, **kw))
+    if a.recurrent:
+        from robot_lab_amd.distill_recurrent import RecurrentDistillation
+        from robot_lab_amd.distill_recurrent_hip import HipRecurrentDistillation
+
+        learners = dict(torch=RecurrentDistillation(copy.deepcopy(tr.policy), **kw), hip=HipRecurrentDistillation(copy.deepcopy(tr.policy), num_envs=a.num_envs, **kw))
+    else:
+        learners = dict(torch=Distillation(copy.deepcopy(tr.policy), **kw), hip=HipDistillation(copy.deepcopy(tr.policy), num_envs=a.num_envs, **kw))
     for _ in range(a.warmup):
         for alg in learners.values():
             alg.update(batch)
@@ -77,7 +98,8 @@ def main():
     for _ in range(a.repeat):
         for k, alg in learners.items():
             times[k].append(timed(lambda: alg.update(batch)))  # noqa: B023
-    out = dict(task=a.task, num_envs=a.num_envs, steps=a.steps, student=[128, 128, 128], **{k: v for k, v in kw.items()},
+    out = dict(task=a.task, num_envs=a.num_envs, steps=a.steps, student=[128, 128, 128], recurrent=a.recurrent, teacher_recurrent=rnn_teacher,
+               **{k: v for k, v in kw.items()},
                optimiser_steps_per_update=learners["hip"].num_updates, update={k: spread(v) for k, v in times.items()},
                hip_over_torch=statistics.median(times["hip"]) / statistics.median(times["torch"]),
                collect=dict(eager=spread(collect[False]), graph=spread(collect[True])),
@@ -85,7 +107,8 @@ def main():
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
-            f.write(f"tools/bench_distill.py: {a.task}, {a.num_envs} envs x {a.steps} steps, student 128-128-128, gradient length 15, 2 epochs "
+            f.write(f"tools/bench_distill.py{' --recurrent' if a.recurrent else ''}{' --mlp-teacher' if a.mlp_teacher else ''}: {a.task}, {a.num_envs} envs x "
+                    f"{a.steps} steps, student {'LSTM 256 + ' if a.recurrent else ''}128-128-128, gradient length 15, 2 epochs "
                     f"({out['optimiser_steps_per_update']} optimiser steps per update); {a.repeat} alternating windows after {a.warmup} warm-up updates\n")
             for k, v in out["update"].items():
                 f.write(f"update   {k:<6} median {v['median_ms']:9.3f} ms   min {v['min_ms']:9.3f}   max {v['max_ms']:9.3f}\n")

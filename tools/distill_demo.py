@@ -9,7 +9,10 @@ distil it" recipe (the reference's `train.py --agent=rsl_rl_distillation_cfg_ent
 A1 Flat with the numbers of the reference's rsl_rl_distillation_cfg.py: student 128-128-128, 120 steps per env, gradient length 15, two epochs,
 learning rate 1e-3, init_std 0.1.  The teacher is a checkpoint in the runner's layout, e.g. of `tools/train_demo.py --save teacher.pt`
 (its actor becomes the teacher; the teacher's hidden widths are read from it).
-    python tools/distill_demo.py --teacher model.pt [--learner torch|hip] [--iterations n] [--num-envs N] [--save PATH]"""
+`--recurrent`: a recurrent student (an LSTM of 256 in front of the 128-128-128 MLP, robot_lab_amd/distill_recurrent.py) and the teacher of a
+recurrent PPO checkpoint (`tools/train_demo.py --recurrent --save teacher.pt`: its memory_a and actor); `--mlp-teacher`: a feed-forward teacher's
+checkpoint distilled into the recurrent student.
+    python tools/distill_demo.py --teacher model.pt [--recurrent [--mlp-teacher]] [--learner torch|hip] [--iterations n] [--num-envs N] [--save PATH]"""
 import argparse
 import json
 import os
@@ -32,18 +35,32 @@ def main():
     ap.add_argument("--learner", choices=("torch", "hip"), default="torch")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--save", default=None, metavar="PATH", help="write the distilled policy as a checkpoint in the runner's layout")
+    ap.add_argument("--recurrent", action="store_true", help="a recurrent student; the teacher is a recurrent PPO checkpoint unless --mlp-teacher")
+    ap.add_argument("--mlp-teacher", action="store_true", help="with --recurrent: the teacher is a feed-forward PPO checkpoint")
     a = ap.parse_args()
+    if a.mlp_teacher and not a.recurrent:
+        ap.error("--mlp-teacher goes with --recurrent")
     d = torch.load(a.teacher, map_location="cpu", weights_only=False)
     sd = d["model_state_dict"] if "model_state_dict" in d else d
-    layers = sorted(int(k.split(".")[1]) for k in sd if k.startswith("actor.") and k.endswith(".weight"))
+    net = "actor" if any(k.startswith("actor.") for k in sd) else "teacher"  # (a distillation checkpoint resumes)
+    layers = sorted(int(k.split(".")[1]) for k in sd if k.startswith(net + ".") and k.endswith(".weight"))
     if not layers:
         ap.error(f"{a.teacher} holds no actor.* keys: not a PPO checkpoint")
-    teacher_hidden = tuple(int(sd[f"actor.{i}.weight"].shape[0]) for i in layers[:-1])
+    teacher_hidden = tuple(int(sd[f"{net}.{i}.weight"].shape[0]) for i in layers[:-1])
+    rkw = {}
+    if a.recurrent:
+        has_memory = any(k.startswith(("memory_a.", "memory_t.")) for k in sd)
+        if has_memory == a.mlp_teacher:
+            ap.error(f"{a.teacher} holds " + ("a recurrent teacher: drop --mlp-teacher" if has_memory else "no memory_a.* keys: a feed-forward teacher goes with --mlp-teacher"))
+        H = int(sd["memory_a.rnn.weight_hh_l0" if "memory_a.rnn.weight_hh_l0" in sd else "memory_t.rnn.weight_hh_l0"].shape[1]) if has_memory else 256
+        rkw = dict(rnn_type="lstm", rnn_hidden_dim=H, teacher_recurrent=has_memory)
+    elif any(k.startswith("memory_a.") for k in sd):
+        ap.error(f"{a.teacher} is a recurrent PPO checkpoint: pass --recurrent")
     env = ManagerBasedRLEnv(a.task, num_envs=a.num_envs, seed=a.seed, device="cuda:0")
     print(env, flush=True)
     tr = DistillTrainer(env, num_steps_per_env=120, student_hidden=(128, 128, 128), teacher_hidden=teacher_hidden, init_noise_std=0.1, learner=a.learner,
                         teacher_obs_normalization=any(k.startswith("actor_obs_normalizer.") for k in sd), seed=a.seed,
-                        num_learning_epochs=2, gradient_length=15, learning_rate=1e-3)
+                        num_learning_epochs=2, gradient_length=15, learning_rate=1e-3, **rkw)
     resumed = tr.load_state_dict(sd)
     print(tr, f"teacher {teacher_hidden} from {a.teacher}" + (" (a distillation checkpoint: resumed)" if resumed else ""), flush=True)
     env.episode_length_buf = torch.randint(0, env.max_episode_length, (a.num_envs,), generator=torch.Generator().manual_seed(a.seed))
@@ -57,7 +74,7 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     steps = a.iterations * 120 * a.num_envs
-    print(json.dumps(dict(task=a.task, learner=a.learner, num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps_per_s=steps / wall,
+    print(json.dumps(dict(task=a.task, learner=a.learner, recurrent=a.recurrent, teacher_recurrent=bool(rkw.get("teacher_recurrent")), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps_per_s=steps / wall,
                           behavior_first=log[0]["behavior"], behavior_last=log[-1]["behavior"], falling=log[-1]["behavior"] < log[0]["behavior"])))
     if a.save:
         opt = tr.alg.optimizer_state_dict() if a.learner == "hip" else tr.alg.optimizer.state_dict()
