@@ -35,9 +35,22 @@ class Collector:
 
     def __init__(self, env, actor, critic, storage, action_std: torch.Tensor, gamma: float = 0.99, lam: float = 0.95,
                  normalize_advantage: bool = True, use_graph: bool = True, clip_actions: float | None = None, overlap: bool = False, critic_small: bool = True,
-                 fused_act: bool | None = None, normalizers=None, recurrent=None):
+                 fused_act: bool | None = None, normalizers=None, recurrent=None, rnd=None):
         self.env, self.actor, self.critic, self.storage = env, actor, critic, storage
         self.overlap = overlap
+        # a robot_lab_amd.rnd_hip.RndDevice: the intrinsic reward of random network distillation behind every env.step - see `_iteration_rnd`
+        self.rnd = rnd
+        if rnd is not None:
+            if overlap:
+                raise NotImplementedError("Collector: overlap=True with rnd= is not implemented: the critic's side stream reads the observation buffer that the "
+                                          "RND launches of the same step read on the main stream, and the deferred bootstrap would be added after the intrinsic "
+                                          "reward; use the serial loop (overlap=False)")
+            if recurrent is not None or (normalizers is not None and any(n is not None for n in normalizers)):
+                raise NotImplementedError("Collector: rnd= with recurrent= or normalizers= is not implemented: the RND loop is the fused-act loop, which has "
+                                          "neither the cells' nor the normalisers' launches; drop one of them")
+            if rnd.num_envs != storage.num_envs or rnd.num_steps != storage.num_transitions_per_env:
+                raise ValueError(f"Collector: the RndDevice is sized {rnd.num_steps} x {rnd.num_envs}, the storage "
+                                 f"{storage.num_transitions_per_env} x {storage.num_envs}")
         # a robot_lab_amd.lstm.RecurrentState: the memories in front of `actor` / `critic` (MLP heads of input width H) - see `_iteration_recurrent`
         self.recurrent = recurrent
         if recurrent is not None:
@@ -90,6 +103,8 @@ class Collector:
             return self._iteration_normalized(obs)
         if self.recurrent is not None:
             return self._iteration_recurrent(obs)
+        if self.rnd is not None:
+            return self._iteration_rnd(obs)
         st, env = self.storage, self.env
         st.clear()
         for _ in range(self.T):
@@ -101,6 +116,27 @@ class Collector:
                 if self.clip_actions is not None:
                     actions = actions.clamp(-self.clip_actions, self.clip_actions)
             obs, _, _, _, _ = env.step(actions, rollout=st, gamma=self.gamma)
+        st.compute_returns(self.critic(obs["critic"]), self.gamma, self.lam, self.normalize)
+        return obs
+
+    def _iteration_rnd(self, obs):
+        """The fused-act loop with the RND launches behind env.step (THE RULE: robot_lab_amd/rnd.py `collect_step`): the env kernel has written
+        r_ext + gamma V on time-outs into the reward slot of step t, then the NEW observations o_{t+1} of the RND group - post-reset rows for envs
+        that were done - go through the state normaliser (update, then apply), the predictor / target pair launch and the reward kernels
+        (csrc/rl_rnd.hip), which add weight_t r_int into the same slot.  GAE therefore sees the sum.  The weights of the iteration are a device
+        vector filled ahead of the loop (`collect`), so every launch argument of a step is fixed and the loop is captured like the plain one."""
+        st, env, rnd = self.storage, self.env, self.rnd
+        st.clear()
+        for t in range(self.T):
+            if self.fused_act:
+                actions = st.act_fused(self.actor, self.critic, obs["policy"], obs["critic"], self.std, self.clip_actions)
+            else:
+                mean, values = self.actor.forward_pair(obs["policy"], self.critic, obs["critic"])
+                actions = st.act(obs["policy"], obs["critic"], mean, self.std, values)
+                if self.clip_actions is not None:
+                    actions = actions.clamp(-self.clip_actions, self.clip_actions)
+            obs, _, _, _, _ = env.step(actions, rollout=st, gamma=self.gamma)
+            rnd.step(t, obs[rnd.group], st.rewards[t])
         st.compute_returns(self.critic(obs["critic"]), self.gamma, self.lam, self.normalize)
         return obs
 
@@ -199,6 +235,8 @@ class Collector:
     @torch.inference_mode()
     def collect(self):
         """One iteration: fills the storage (observations ... advantages) and returns the observations of the next one."""
+        if self.rnd is not None:  # the [T] weights of this iteration: a stream-ordered copy ahead of the loop (eager or replayed)
+            self.rnd.begin_iteration()
         if not self.use_graph:
             self.obs = self._iteration(self.obs)
             return self.obs

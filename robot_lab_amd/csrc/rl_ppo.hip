@@ -1159,3 +1159,6 @@ int rl_ppo_stats_ex(rl_ppo* p, double* out, int32_t n_out, void* stream) {
 // the recurrent distillation learner (include/rl_distill_bptt.h): behind both, since it launches the distillation learner's head and the recurrent
 // learner's step kernels
 #include "learner/rl_distill_bptt.inl"
+
+// the update of random network distillation (include/rl_rnd_learner.h): a new sequence of the kernels above and of the distillation learner's head
+#include "learner/rl_rnd.inl"

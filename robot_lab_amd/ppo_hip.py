@@ -130,10 +130,19 @@ class HipPPO:
     def __init__(self, policy, value_loss_coef=1.0, use_clipped_value_loss=True, clip_param=0.2, entropy_coef=0.01, num_learning_epochs=5,
                  num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", desired_kl=0.01, max_grad_norm=1.0, group=None,
                  max_rows_per_minibatch=None, lib_path: str | None = None, symmetry=None, mirror_loss=None, data_augmentation=True,
-                 obs_normalizers=None):
+                 obs_normalizers=None, rnd=None):
         import torch
 
         from .ppo import check_mirror_loss
+
+        # random network distillation: a robot_lab_amd.rnd_hip.HipRND, whose update is enqueued behind this learner's with the same permutation
+        if rnd is not None:
+            if not (callable(getattr(rnd, "update", None)) and callable(getattr(rnd, "stats", None)) and hasattr(rnd, "group")):
+                raise TypeError(f"HipPPO: rnd must be a robot_lab_amd.rnd_hip.HipRND (or None), not {type(rnd).__name__}")
+            if symmetry is not None or (group is not None and getattr(group, "enabled", False)):
+                raise NotImplementedError("HipPPO: rnd= with symmetry= or an enabled group is not implemented (the predictor neither trains on mirrored copies "
+                                          "nor exchanges gradients)")
+        self.rnd = rnd
 
         if group is not None and not (isinstance(getattr(group, "world_size", None), int) and hasattr(group, "enabled") and callable(getattr(group, "all_reduce_sum", None))):
             raise NotImplementedError(f"HipPPO: group={type(group).__name__} has no world_size / enabled / all_reduce_sum(tensor): the HIP learner's multi-GPU "
@@ -459,6 +468,13 @@ class HipPPO:
                         raise RlPpoError(f"HipPPO.update: the group's all_reduce_sum failed in mini-batch {i} ({type(e).__name__}: {e}); the learner's "
                                          "replicas can no longer be in step, so this learner is CLOSED - build a new one and load the last checkpoint") from e
                     self._check(self.lib.rl_ppo_minibatch_apply(self.handle, stream))
+        if self.rnd is not None:
+            # THE RULE takes the predictor's step right behind the PPO step of each mini-batch; the two touch disjoint state (the target and the
+            # normaliser's statistics are constants of the update), so all PPO mini-batches followed by all RND mini-batches over the SAME perm give
+            # the same bits - and the PPO half is the launch sequence of a learner without rnd=
+            from .rnd import storage_state
+
+            self.rnd.update(storage_state(storage, self.rnd.group), perm, checked=True)
         # the one wait of the update (keeps `keep` / `perm` alive until then)
         if self.mirror_loss is None:
             out = (C.c_double * 8)()
@@ -470,6 +486,8 @@ class HipPPO:
         res = dict(value_loss=float(out[0]), surrogate_loss=float(out[1]), entropy=float(out[2]), kl=float(out[3]))
         if self.mirror_loss is not None:
             res["mirror_loss"] = float(out[8])
+        if self.rnd is not None:
+            res.update(self.rnd.stats())  # (the stream has been waited for: a small copy)
         res["learning_rate"] = self.learning_rate
         return res
 

@@ -22,6 +22,38 @@ class RslRlPpoActorCriticCfg:
 
 
 @configclass
+class RslRlRndCfg:
+    """[UPSTREAM isaaclab_rl.rsl_rl.rnd_cfg] random network distillation, IsaacLab's field names; read by robot_lab_amd.rnd.read_rnd_cfg.  The state
+    the networks see is `obs_groups["rnd_state"]` of the runner cfg (one group)."""
+
+    @configclass
+    class WeightScheduleCfg:
+        mode: str = "constant"
+
+    @configclass
+    class LinearWeightScheduleCfg(WeightScheduleCfg):
+        mode: str = "linear"
+        final_value: float = MISSING
+        initial_step: int = MISSING
+        final_step: int = MISSING
+
+    @configclass
+    class StepWeightScheduleCfg(WeightScheduleCfg):
+        mode: str = "step"
+        final_step: int = MISSING
+        final_value: float = MISSING
+
+    weight: float = 0.0
+    weight_schedule = None
+    reward_normalization: bool = False
+    state_normalization: bool = False
+    learning_rate: float = 1e-3
+    num_outputs: int = 1
+    predictor_hidden_dims: list = [-1]
+    target_hidden_dims: list = [-1]
+
+
+@configclass
 class RslRlPpoAlgorithmCfg:
     class_name: str = "PPO"
     num_learning_epochs: int = MISSING

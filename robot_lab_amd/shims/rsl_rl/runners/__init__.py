@@ -13,7 +13,9 @@ rsl_rl's `actor_obs_normalizer.*` / `critic_obs_normalizer.*` buffers.
 A recurrent cfg - `policy.class_name="ActorCriticRecurrent"`, or the reference's `actor=` / `critic=` RNNModel cfgs (robot_lab_amd.recurrent.read_recurrent_cfg) -
 builds `Trainer(rnn_type="lstm", ...)`: the LSTM cells run in the captured collection (csrc/rl_lstm.hip), the update is the torch learner's or - with
 `RL_RECURRENT_LEARNER=hip` in the environment - back-propagation through time on the HIP learner of robot_lab_amd/recurrent_hip.py; checkpoints carry
-rsl_rl's `memory_a.rnn.*` / `memory_c.rnn.*` keys, `get_inference_policy()` is stateful with `reset(dones)`."""
+rsl_rl's `memory_a.rnn.*` / `memory_c.rnn.*` keys, `get_inference_policy()` is stateful with `reset(dones)`.
+`algorithm.rnd_cfg` (IsaacLab's `RslRlRndCfg` fields) with `obs_groups["rnd_state"]` builds `Trainer(rnd=...)`: random network distillation with either learner;
+checkpoints then carry rsl_rl's `rnd_state_dict` / `rnd_optimizer_state_dict`."""
 from __future__ import annotations
 
 import os
@@ -71,8 +73,11 @@ class OnPolicyRunner:
             raise NotImplementedError("stand-in runner: a symmetry_cfg carries an arbitrary Python data_augmentation_func, which cannot be turned into the "
                                       "learners' tables; symmetry data augmentation and the mirror loss inside the update are "
                                       f"robot_lab_amd.ppo.Trainer(env, symmetry=\"lr\" | \"lr,fb\" | SymmetryTables{mirror}) (INTEGRATION.md section 7)")
-        if alg.get("rnd_cfg"):
-            raise NotImplementedError("stand-in runner: RND is not wired into the update")
+        # random network distillation: `algorithm.rnd_cfg` (IsaacLab's RslRlRndCfg fields) + `obs_groups["rnd_state"]` -> Trainer(rnd=...); what it does
+        # not combine with is refused by the reader / the Trainer with a reason (robot_lab_amd/rnd.py)
+        from robot_lab_amd.rnd import read_rnd_cfg
+
+        rnd = read_rnd_cfg(train_cfg)
         # options this stand-in does not implement are refused, never ignored (a silently different learner is worse than none)
         groups = dict(train_cfg.get("obs_groups") or {})
         actor_set = groups.get("policy", groups.get("actor", ["policy"]))
@@ -97,7 +102,8 @@ class OnPolicyRunner:
                                lam=float(alg.get("lam", 0.95)), seed=int(train_cfg.get("seed", 42)), actor_hidden=pol.get("actor_hidden_dims", (512, 256, 128)),
                                critic_hidden=pol.get("critic_hidden_dims", (512, 256, 128)), init_noise_std=float(pol.get("init_noise_std", 1.0)),
                                clip_actions=getattr(env, "clip_actions", None), group=self.group if self.group.enabled else None, learner=self.learner,
-                               **{k: v for k, v in norm.items() if v}, **(recurrent or {}), **{k: alg[k] for k in keys if k in alg})
+                               **{k: v for k, v in norm.items() if v}, **(recurrent or {}), **({"rnd": rnd} if rnd is not None else {}),
+                               **{k: alg[k] for k in keys if k in alg})
         self.alg = self.trainer.alg
         # the learner keeps master parameters and Adam's state on the device (HipPPO, or - RL_RECURRENT_LEARNER=hip - HipRecurrentPPO: the same methods)
         self._device_learner = self.learner == "hip" or (recurrent is not None and recurrent.get("recurrent_learner") == "hip")
@@ -147,6 +153,8 @@ class OnPolicyRunner:
             self.last_episode_log = ep = episode_log.result()
             print(f"[rsl_rl stand-in] iteration {it + 1}/{start + num_learning_iterations}  mean reward/step {out['mean_reward']:+.4f}  value loss {out['value_loss']:.4f}  "
                   f"surrogate {out['surrogate_loss']:+.4f}  std {out['action_std']:.3f}  lr {out['learning_rate']:.1e}  "
+                  + (f"rnd loss {out['rnd_loss']:.3e}  intrinsic {out['mean_intrinsic_reward']:+.4f}  extrinsic {out['mean_extrinsic_reward']:+.4f}  "
+                     f"rnd weight {out['rnd_weight']:.3g}  " if "rnd_loss" in out else "") +
                   f"{steps * (it + 1 - start) / max(time.time() - t0, 1e-9):.0f} steps/s  "
                   f"episode log over {int(ep['num_envs'])} envs ({int(ep['episodes'])} episodes ended)"
                   + (f"  terrain level {float(ep['Curriculum/terrain_levels']):.2f}" if "Curriculum/terrain_levels" in ep else ""), flush=True)
@@ -167,12 +175,20 @@ class OnPolicyRunner:
         else:
             optimizer_state = self.alg.optimizer.state_dict()
         self.trainer.sync_normalizers()  # the running statistics live on the device: into the module's buffers (rsl_rl's keys)
-        torch.save({"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": optimizer_state,
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        saved = {"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": optimizer_state,
+                 "iter": self.current_learning_iteration, "infos": infos}
+        if self.trainer.rnd is not None:  # rsl_rl's keys; the optimiser's in torch.optim.Adam's layout with either learner
+            saved["rnd_state_dict"] = self.trainer.rnd_state_dict()
+            saved["rnd_optimizer_state_dict"] = self.trainer.rnd_optimizer_state_dict()
+        torch.save(saved, path)
 
     def load(self, path: str, load_optimizer: bool = True, map_location=None):
         d = torch.load(path, map_location=map_location or self.trainer.device, weights_only=False)
         self.alg.policy.load_state_dict(d["model_state_dict"])  # strict: normaliser keys the flags do not ask for - or miss - raise here
+        if self.trainer.rnd is not None:
+            if "rnd_state_dict" not in d:
+                raise KeyError(f"{path} has no rnd_state_dict: it was written by a run without rnd_cfg")
+            self.trainer.load_rnd_state(d["rnd_state_dict"], d.get("rnd_optimizer_state_dict") if load_optimizer else None)
         if self._device_learner:
             self.alg.load_from(self.alg.policy)
             if load_optimizer and d.get("optimizer_state_dict"):

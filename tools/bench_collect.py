@@ -10,7 +10,9 @@ depend on them.
 --obs-normalization: empirical normalisation of both groups (csrc/rl_obsnorm.hip) against the fused-act loop and against the unfused loop
 (actor + critic, then the act kernel) it is built on, alternating windows of this process.
 --recurrent: the recurrent loop (two LSTM cells of H = 256 in one launch, csrc/rl_lstm.hip, in front of 128-128-128 heads, unfused act) against the
-feed-forward fused-act loop (512-256-128 networks) and the feed-forward unfused loop, alternating windows of this process."""
+feed-forward fused-act loop (512-256-128 networks) and the feed-forward unfused loop, alternating windows of this process.
+--rnd: random network distillation behind every env.step (csrc/rl_rnd.hip; predictor and target 256-256 -> 1 on the policy group) without and with
+both of its normalisers, against the fused-act loop it is built on, alternating windows of this process."""
 import os
 import sys
 import time
@@ -34,6 +36,9 @@ if ap_norm:
 ap_rec = "--recurrent" in sys.argv
 if ap_rec:
     sys.argv.remove("--recurrent")
+ap_rnd = "--rnd" in sys.argv
+if ap_rnd:
+    sys.argv.remove("--rnd")
 task = sys.argv[1] if len(sys.argv) > 1 else "RobotLab-Isaac-Velocity-Rough-Unitree-A1-v0"
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 ITERS = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -46,7 +51,7 @@ FUSED_ACT = os.environ.get("RL_FUSED_ACT", "1") == "1"  # sampling / log-prob / 
 OVERLAP = os.environ.get("RL_OVERLAP", "0") == "1"  # the critic of step t on a second stream under env step t (0: actor + critic as one launch in front of act)
 
 
-def setup(hist, norm=False, fused_act=FUSED_ACT, recurrent=False):
+def setup(hist, norm=False, fused_act=FUSED_ACT, recurrent=False, rnd=None):
     """-> (env, storage, iteration(obs) -> obs) of one collection loop; `hist`: policy-group history length (0: none); `norm`: both groups normalised;
     `recurrent`: LSTM cells of H = 256 in front of 128-128-128 heads (the reference's recurrent agent cfgs)"""
     env = ManagerBasedRLEnv(task, num_envs=N, seed=42, device="cuda:0", obs_history={"policy": hist} if hist else None)
@@ -72,6 +77,17 @@ def setup(hist, norm=False, fused_act=FUSED_ACT, recurrent=False):
         rec = RecurrentState(cell(od), cell(cd), N, T)
         col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, recurrent=rec)
         return env, storage, (lambda obs: col.collect()), (actor, critic, col, rec)
+    if rnd is not None:  # `rnd`: normalisers on / off; rsl_rl's defaults otherwise (one output), 256-256 networks on the policy group
+        from robot_lab_amd.collect import Collector  # noqa: E402
+        from robot_lab_amd.rnd import RandomNetworkDistillation  # noqa: E402
+        from robot_lab_amd.rnd_hip import RndDevice  # noqa: E402
+
+        torch.manual_seed(0)
+        module = RandomNetworkDistillation(od, num_outputs=1, predictor_hidden_dims=(256, 256), target_hidden_dims=(256, 256), weight=0.1, state_normalization=rnd,
+                                           reward_normalization=rnd).to("cuda:0")
+        dev = RndDevice(module, N, T, device="cuda:0")
+        col = Collector(env, actor, critic, storage, std, GAMMA, LAM, use_graph=True, rnd=dev)
+        return env, storage, (lambda obs: col.collect()), (actor, critic, col, dev)
     if GRAPH and FUSED and PAIR:
         from robot_lab_amd.collect import Collector  # noqa: E402
 
@@ -175,6 +191,37 @@ if ap_norm:
     count = int(sides["normalized"]["keep"][3][0].get_state()[3])
     ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values()) and count > 0
     print(f"finite: {ok}; rows seen by the policy group's statistics: {count}")
+    sys.exit(0 if ok else 1)
+
+if ap_rnd:
+    # the fused-act loop (RND off), RND without normalisers (2 launches per step more: the predictor / target pair, the one reward kernel) and RND with
+    # both normalisers (6 more: + state update and apply, + the dim-1 update with avg and the finish kernel), alternating steady-state windows in ONE process
+    ROUNDS = 6
+    kinds = {"rnd_off": dict(), "rnd": dict(rnd=False), "rnd_normalized": dict(rnd=True)}
+    sides = {}
+    with torch.inference_mode():
+        for name, kw in kinds.items():
+            env, storage, iteration, keep = setup(0, **kw)
+            obs = env.get_observations()
+            for _ in range(3):
+                obs = iteration(obs)
+            sides[name] = dict(env=env, storage=storage, iteration=iteration, keep=keep, obs=obs, collect=[])
+        order = list(kinds)
+        for r in range(ROUNDS):
+            for name in (order if r % 2 == 0 else order[::-1]):
+                sd = sides[name]
+                dt, sd["obs"] = window(sd["iteration"], sd["obs"], ITERS)
+                sd["collect"].append(1e6 * dt / ITERS / T)
+    for name, sd in sides.items():
+        v = np.array(sd["collect"])
+        print(f"{task} N={N} {name:15s} collect us/step: windows {np.round(v, 2).tolist()} median {np.median(v):.2f} min {v.min():.2f} max {v.max():.2f}")
+    med = {name: float(np.median(sd["collect"])) for name, sd in sides.items()}
+    print(f"{task} N={N}: RND costs {med['rnd'] - med['rnd_off']:+.2f} us/step ({100 * (med['rnd'] - med['rnd_off']) / med['rnd_off']:+.1f} %) over the fused-act loop "
+          f"(the pair launch + the reward kernel), {med['rnd_normalized'] - med['rnd_off']:+.2f} ({100 * (med['rnd_normalized'] - med['rnd_off']) / med['rnd_off']:+.1f} %) with both "
+          f"normalisers (+ update, apply, update of the reward statistics, finish) (medians of {ROUNDS} alternating windows)")
+    sums = sides["rnd_normalized"]["keep"][3].reward.sums()
+    ok = all(bool(torch.isfinite(sd["storage"].advantages).all()) for sd in sides.values()) and sums[0] > 0
+    print(f"finite: {ok}; mean intrinsic reward of the last iteration {sums[0] / (T * N):.4f}")
     sys.exit(0 if ok else 1)
 
 if ap_rec:

@@ -155,6 +155,43 @@ def bench_one(tr, tab, repeat, warmup, seed, split=False, **kw):
     return res
 
 
+def bench_rnd(task, num_envs, repeat, warmup, seed=42):
+    """One update with and without random network distillation (predictor / target 256-256 -> 1 on the policy group, state normalisation on) on either
+    learner, the four learners alternating on ONE collected batch: median ms per update and what RND adds."""
+    from robot_lab_amd.rnd_hip import HipRND
+
+    env = ManagerBasedRLEnv(task, num_envs=num_envs, seed=seed, device="cuda:0")
+    tr = Trainer(env, seed=seed, rnd=dict(weight=0.1, state_normalization=True, reward_normalization=True, predictor_hidden_dims=[256, 256], target_hidden_dims=[256, 256]))
+    tr.collector.collect()
+    batch = tr.update_batch()
+    torch.cuda.synchronize()
+    st = tr.storage
+    rows = st.num_transitions_per_env * st.num_envs
+    hip_rnd = HipRND(copy.deepcopy(tr.rnd), 5, 4, rows // 4, state_normalizer=tr.rnd_device.state_norm)
+    learners = {"torch": PPO(copy.deepcopy(tr.policy)), "torch_rnd": PPO(copy.deepcopy(tr.policy), rnd=copy.deepcopy(tr.rnd)),
+                "hip": HipPPO(copy.deepcopy(tr.policy)), "hip_rnd": HipPPO(copy.deepcopy(tr.policy), rnd=hip_rnd)}
+    gens = {k: torch.Generator(device="cuda:0").manual_seed(seed) for k in learners}
+    times = {k: [] for k in learners}
+    for it in range(warmup + repeat):
+        for k, alg in learners.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            out = alg.update(batch, gens[k])
+            t1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                times[k].append(t0.elapsed_time(t1))
+            assert all(v == v for v in out.values()), (k, out)  # no NaN
+    res = dict(task=task, num_envs=num_envs, rows=rows, repeat=repeat, warmup=warmup, rnd="256-256 -> 1, state normalisation")
+    for k, t in times.items():
+        res[k] = dict(median_ms=statistics.median(t), min_ms=min(t), max_ms=max(t))
+    res["torch_rnd_adds_ms"] = res["torch_rnd"]["median_ms"] - res["torch"]["median_ms"]
+    res["hip_rnd_adds_ms"] = res["hip_rnd"]["median_ms"] - res["hip"]["median_ms"]
+    learners["hip"].close(); learners["hip_rnd"].close(); hip_rnd.close(); env.close()
+    return res
+
+
 def recurrent_flops(alg, rows: int) -> float:
     """2 flops per multiply-add x rows x epochs x (the memories: W_ih forward + dW, W_hh forward + dX + dW; the heads: forward + dX + dW per layer - the
     first layer's dX is dL/dh)"""
@@ -213,7 +250,16 @@ def main():
                     help="normalise both observation groups: in a pass before every update (scratch) or inside the learners (learner)")
     ap.add_argument("--recurrent", action="store_true", help="time the recurrent update: the torch rule against the HIP learner's back-propagation through time")
     ap.add_argument("--rnn-hidden-dim", type=int, default=256)
+    ap.add_argument("--rnd", action="store_true", help="time one update with and without random network distillation on either learner")
     a = ap.parse_args()
+    if a.rnd:
+        if a.symmetry != ["off"] or a.mirror_loss is not None or a.split or a.obs_normalization or a.recurrent:
+            ap.error("--rnd does not combine with --symmetry, --mirror-loss, --split, --obs-normalization or --recurrent (Trainer(rnd=...) refuses them)")
+        if len(a.num_envs) != len(a.task):
+            ap.error("one --num-envs per --task")
+        for task, n in zip(a.task, a.num_envs):
+            print(json.dumps(bench_rnd(task, n, a.repeat, a.warmup)), flush=True)
+        return
     if a.recurrent:
         if a.symmetry != ["off"] or a.mirror_loss is not None or a.split or a.obs_normalization:
             ap.error("--recurrent does not combine with --symmetry, --mirror-loss, --split or --obs-normalization (the recurrent learners refuse them)")

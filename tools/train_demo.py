@@ -50,6 +50,10 @@ def main():
     ap.add_argument("--rnn-hidden-dim", type=int, default=256, metavar="H", help="with --recurrent: the LSTM's hidden width")
     ap.add_argument("--recurrent-learner", choices=("torch", "hip"), default="torch",
                     help="with --recurrent: torch autograd through time (robot_lab_amd/recurrent.py) or the HIP learner (robot_lab_amd/recurrent_hip.py)")
+    ap.add_argument("--rnd-weight", type=float, default=None, metavar="W", help="random network distillation (Trainer(rnd=...)): weight of the intrinsic reward; "
+                    "predictor and target 256-256 -> 1 on the policy group")
+    ap.add_argument("--rnd-reward-normalization", action="store_true", help="with --rnd-weight: the intrinsic reward over the running std of its discounted average")
+    ap.add_argument("--rnd-state-normalization", action="store_true", help="with --rnd-weight: empirical normalisation of the RND state")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out"))
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--save", default=None, metavar="PATH", help="also write a checkpoint in the runner's layout (model_state_dict / optimizer_state_dict / iter / infos): "
@@ -62,6 +66,8 @@ def main():
         ap.error("--normalize-in-learner needs --obs-normalization")
     if a.recurrent_learner != "torch" and not a.recurrent:
         ap.error("--recurrent-learner needs --recurrent")
+    if a.rnd_weight is None and (a.rnd_reward_normalization or a.rnd_state_normalization):
+        ap.error("--rnd-reward-normalization / --rnd-state-normalization need --rnd-weight")
     hist = {"policy": a.obs_history} if a.obs_history else None
     if a.also_terminate_on:
         import re
@@ -82,7 +88,9 @@ def main():
     norm = dict(actor_obs_normalization=True, critic_obs_normalization=True, normalize_in_learner=a.normalize_in_learner) if a.obs_normalization else {}
     rnn = dict(rnn_type="lstm", rnn_hidden_dim=a.rnn_hidden_dim, actor_hidden=(128, 128, 128), critic_hidden=(128, 128, 128), recurrent_learner=a.recurrent_learner) if a.recurrent else {}
     device_learner = a.learner == "hip" or (a.recurrent and a.recurrent_learner == "hip")  # the std the sampler reads and Adam's state live in the learner
-    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror, **norm, **rnn)
+    rnd = dict(rnd=dict(weight=a.rnd_weight, reward_normalization=a.rnd_reward_normalization, state_normalization=a.rnd_state_normalization,
+                        predictor_hidden_dims=[256, 256], target_hidden_dims=[256, 256])) if a.rnd_weight is not None else {}
+    tr = Trainer(env, seed=a.seed, learner=a.learner, symmetry=a.symmetry, **mirror, **norm, **rnn, **rnd)
     print(tr, flush=True)
     # init_at_random_ep_len=True (train.py:224): the first time-outs are spread over an episode length
     env.episode_length_buf = torch.randint(0, env.max_episode_length, (a.num_envs,), generator=torch.Generator().manual_seed(a.seed))
@@ -98,6 +106,9 @@ def main():
         t1 = time.perf_counter()
         st = tr.storage
         row = dict(iteration=it, mean_step_reward=float(st.rewards.mean()), done_rate=float(st.dones.float().mean()))
+        if tr.rnd_device is not None:
+            intrinsic, total = tr.rnd_device.reward.sums()
+            row.update(mean_intrinsic_reward=intrinsic / st.rewards.numel(), mean_extrinsic_reward=(total - intrinsic) / st.rewards.numel(), rnd_weight=tr.rnd_device.last_weight)
         row.update(tr.alg.update(tr.update_batch(), tr.gen))
         tr.push_parameters()
         torch.cuda.synchronize()
@@ -119,15 +130,17 @@ def main():
         if it % a.print_every == 0 or it == a.iterations - 1:
             print(f"it {it:4d}  reward/step {row['mean_step_reward']:+.4f}  {track} {row.get('Episode_Reward/' + track, float('nan')):.3f}  "
                   f"err_xy {row.get('Metrics/base_velocity/error_vel_xy', float('nan')):.3f}  done/step {row['done_rate']:.4f}  std {row['action_std']:.3f}  "
-                  f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
+                  f"lr {row['learning_rate']:.1e}  kl {row['kl']:.4f}  v_loss {row['value_loss']:.4f}  "
+                  + (f"rnd_loss {row['rnd_loss']:.3e}  r_int {row['mean_intrinsic_reward']:+.4f}  r_ext {row['mean_extrinsic_reward']:+.4f}  " if "rnd_loss" in row else "") +
+                  f"height {row.get('root_height', float('nan')):.3f}  upright {row.get('upright', float('nan')):+.3f}", flush=True)
     wall = time.perf_counter() - t_start
     n_steps = a.iterations * st.num_transitions_per_env * a.num_envs
-    summary = dict(task=a.task, learner=a.learner, recurrent=bool(a.recurrent), recurrent_learner=a.recurrent_learner if a.recurrent else None, rnn_hidden_dim=a.rnn_hidden_dim if a.recurrent else None, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), normalize_in_learner=bool(a.normalize_in_learner), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
+    summary = dict(task=a.task, learner=a.learner, recurrent=bool(a.recurrent), recurrent_learner=a.recurrent_learner if a.recurrent else None, rnn_hidden_dim=a.rnn_hidden_dim if a.recurrent else None, symmetry=a.symmetry, mirror_loss=a.mirror_loss, data_augmentation=not a.no_data_augmentation, step_kernel=env.step_kernel, obs_history=env.obs_history, obs_normalization=bool(a.obs_normalization), rnd=rnd.get("rnd"), normalize_in_learner=bool(a.normalize_in_learner), num_envs=a.num_envs, iterations=a.iterations, wall_s=wall, env_steps=n_steps, env_steps_per_s=n_steps / wall,
                    collect_ms_per_iteration=1e3 * t_collect / a.iterations, update_ms_per_iteration=1e3 * t_update / a.iterations,
                    first=log[0], last=log[-1])
     print(json.dumps({k: v for k, v in summary.items() if k not in ("first", "last")}))
     os.makedirs(a.out, exist_ok=True)
-    tag = a.task.replace("RobotLab-Isaac-Velocity-", "").replace("-v0", "") + ("_recurrent" if a.recurrent else "") + ("_hip" if a.recurrent and a.recurrent_learner == "hip" else "")
+    tag = a.task.replace("RobotLab-Isaac-Velocity-", "").replace("-v0", "") + ("_recurrent" if a.recurrent else "") + ("_hip" if a.recurrent and a.recurrent_learner == "hip" else "") + ("_rnd" if rnd else "")
     with open(os.path.join(a.out, f"train_demo_{tag}.json"), "w") as f:
         json.dump(dict(summary=summary, log=log), f, indent=1)
     torch.save(tr.state_dict(), os.path.join(a.out, f"train_demo_{tag}.pt"))
